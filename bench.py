@@ -10,10 +10,12 @@ A step = one pass of the whole hot path over one batch resident in HBM (640 clip
 embeddings -> crop/normalise -> ResNet-18 frontend -> AV-HuBERT large encoder (24 layers) -> conformer (12 blocks) ->
 unit/mel heads -> greedy unit decode -> multi-input HiFi-GAN vocoder -> int16 PCM (all on device; weights random-init of
 the reference architecture, data synthetic).  Prints ONE JSON line (rank 0): the real-time factor (audio-seconds per
-wall-second, whole job, inputs resident in HBM), the same with the PCIe transfers inside the timed region
-(`transfer_inclusive`: double-buffered pinned-host -> device frames on a side stream, PCM back to the host), the
-roofline of the dominant kernel (HIP-event timed on the launch stream), whole-step MFMA utilisation and a CPU baseline
-(the oracle, on a bounded sample).
+wall-second, whole job, inputs resident in HBM), `ms_per_step` of the K timed steps and the whole-step MFMA utilisation.
+With --full the line also carries the same with the PCIe transfers inside the timed region (`transfer_inclusive`:
+double-buffered pinned-host -> device frames on a side stream, PCM back to the host), the roofline of the dominant kernel
+(HIP-event timed on the launch stream) and a CPU baseline with a parity sample (the oracle, on a bounded sample).
+--dump-outputs DIR writes what the last timed step computed as DIR/<name>.npy; the inputs and weights are seeded, so two
+builds run with the same arguments can be compared output for output.
 """
 import argparse
 import json
@@ -187,6 +189,37 @@ def build(dtype, device, enc_layers=24, conf_layers=12, seed=0):
     model.to(device).eval()
     voc.to(device).eval()
     return model, voc, sd, vsd
+
+
+DUMP_MAX_BYTES = 64 << 20     # --dump-outputs: all files of a run together
+
+
+def dump_outputs(path, arrays, prefix="", budget=DUMP_MAX_BYTES):
+    """--dump-outputs: every tensor of `arrays` (clip axis first) as path/<prefix><name>.npy, float32 (integer outputs as
+    float64, exact).  An output larger than budget / 16 is written for a fixed, seeded sample of clips only (the same clips for
+    every output and every run), at most 32, halved until the files fit `budget` bytes.  Returns what was written."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    host = {}
+    for k, v in arrays.items():
+        if not torch.is_tensor(v) or v.dim() == 0:
+            continue
+        host[k] = v.detach().cpu().to(torch.float32 if v.is_floating_point() else torch.float64)
+    B = min(v.shape[0] for v in host.values())
+    order = torch.randperm(B, generator=torch.Generator().manual_seed(0))
+    n = min(B, 32)
+    while True:
+        pick = order[:n].sort().values
+        out = {k: v if v.numel() * v.element_size() <= budget // 16 else v[pick] for k, v in host.items()}
+        total = sum(v.numel() * v.element_size() for v in out.values())
+        if total <= budget or n == 1:
+            break
+        n //= 2
+    for k, v in out.items():
+        np.save(os.path.join(path, prefix + k + ".npy"), v.contiguous().numpy())
+    sampled = sorted(k for k in out if out[k].shape[0] != host[k].shape[0])
+    return {"dir": path, "files": sorted(prefix + k + ".npy" for k in out), "bytes": int(total),
+            "sampled": sorted(prefix + k for k in sampled), "sample_clips": pick.tolist() if sampled else None}
 
 
 def _median(xs):
@@ -417,10 +450,14 @@ def bench_mixed(args, pipe, rank, world, dev, sd=None, vsd=None):
     torch.cuda.synchronize()
     per_rank = [round(1e3 * x / args.steps, 3) for x in l2s_dist.all_ranks(own, dev)]
     elapsed = l2s_dist.max_over_ranks(time.perf_counter() - t0, dev)
+    dumped = None
+    if rank == 0 and args.dump_outputs:     # one set of files per length bucket: bucket<i>_<name>.npy
+        dumped = [dump_outputs(args.dump_outputs, w["out"], prefix="bucket%d_" % bi, budget=DUMP_MAX_BYTES // len(work))
+                  for bi, w in enumerate(work)]
     audio_s = float(lengths_all.sum()) / 25.0 * args.steps
     padded = sum(max(w["lens"]) * len(w["lens"]) for w in work)
     roofline, top, cpu, parity = None, [], None, None
-    if rank == 0:
+    if rank == 0 and args.full:
         # dominant kernel over one eager pass of every bucket (per-launch HIP events on the launch stream).  Buckets have
         # different shapes, so per-launch figures are averages over the buckets' launches; no PMC traffic at these shapes
         prof = ops.KernelProfiler()
@@ -430,7 +467,7 @@ def bench_mixed(args, pipe, rank, world, dev, sd=None, vsd=None):
         ops.set_profiler(None)
         roofline, top = dominant_roofline(prof.summary(), passes=1)
         roofline["note"] = "launch shapes differ per length bucket: per-launch figures are means over the buckets"
-    if rank == 0 and world == 1 and not args.no_cpu_baseline and sd is not None:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline and sd is not None:
         # CPU baseline + parity on a bounded sample of THIS workload: warm + timed clips spread evenly over the rank's
         # length-sorted clip list, each run ALONE through the oracle and compared with its row of the batched GPU bucket
         torch.cuda.synchronize()
@@ -463,7 +500,8 @@ def bench_mixed(args, pipe, rank, world, dev, sd=None, vsd=None):
                        "bucket_shapes_rank0": [[len(b), max(b)] for b in buckets], "hipgraph": not args.no_graph, "streams": ns,
                        "padding_overhead_rank0": round(padded / float(sum(my_lens)), 4),
                        "parallelism": f"clip-parallel dp{world}"},
-            "roofline": roofline, "cpu_baseline": cpu, "parity_vs_oracle": parity, "top_kernels": top}), flush=True)
+            "roofline": roofline, "cpu_baseline": cpu, "parity_vs_oracle": parity, "top_kernels": top, "full": args.full,
+            "dumped_outputs": dumped}), flush=True)
     if world > 1:
         torch.distributed.destroy_process_group()
 
@@ -499,14 +537,19 @@ def bench_frontend(args, model, sd, rank, world, dev):
         graph.replay()
         torch.cuda.synchronize()
 
+    last = {"feat": feat}        # what the last step computed (a replayed graph rewrites `feat` in place)
+
     def step_core():
         if graph is not None:
             graph.replay()
         else:
-            step()
+            last["feat"] = step()
 
     step_core()
     elapsed = timed_region(step_core, args.steps, torch.cuda.synchronize, dev)
+    dumped = None
+    if rank == 0 and args.dump_outputs:
+        dumped = dump_outputs(args.dump_outputs, {"features": last["feat"].view(B, T, -1)})
     frames_total = world * B * T * args.steps
     ms_per_step = 1e3 * elapsed / args.steps
     gflop_frame, bytes_frame = 0.6323, 88 * 88 * 2 + 512 * 2
@@ -515,7 +558,7 @@ def bench_frontend(args, model, sd, rank, world, dev):
     ai = gflop_frame * 1e9 / bytes_frame
     ridge = PEAK_MFMA_TFLOPS * 1e12 / (PEAK_HBM_GBS * 1e9)
     roofline = top = cpu = None
-    if rank == 0:
+    if rank == 0 and args.full:
         prof = ops.KernelProfiler()
         ops.set_profiler(prof)
         for _ in range(2):
@@ -559,7 +602,8 @@ def bench_frontend(args, model, sd, rank, world, dev):
                                    "batches, %d clips x %d frames per GPU, 16-bit frames resident in HBM" % (B, T),
                        "clips_per_gpu": B, "frames_per_clip": T, "hipgraph": graph is not None,
                        "parallelism": f"clip-parallel dp{world}"},
-            "roofline": roofline, "cpu_baseline": cpu, "top_kernels": top}), flush=True)
+            "roofline": roofline, "cpu_baseline": cpu, "top_kernels": top, "full": args.full, "dumped_outputs": dumped}),
+            flush=True)
     if world > 1:
         torch.distributed.destroy_process_group()
 
@@ -626,16 +670,19 @@ def bench_latency(args, pipe, dev):
             torch.cuda.synchronize()
             dev_ms.append(e0.elapsed_time(e1))
         dev_ms.sort()
-        prof = ops.KernelProfiler()
-        ops.set_profiler(prof)
-        passes = 5
-        for _ in range(passes):
-            step()
-        ops.set_profiler(None)
-        agg = prof.summary()
-        launches = sum(a["calls"] for a in agg.values()) // passes
-        ksum = sum(a["ms"] for a in agg.values()) / passes
-        roofline, top = dominant_roofline(agg, passes=passes)
+        launches = ksum = roofline = None
+        top = []
+        if args.full:
+            prof = ops.KernelProfiler()
+            ops.set_profiler(prof)
+            passes = 5
+            for _ in range(passes):
+                step()
+            ops.set_profiler(None)
+            agg = prof.summary()
+            launches = sum(a["calls"] for a in agg.values()) // passes
+            ksum = sum(a["ms"] for a in agg.values()) / passes
+            roofline, top = dominant_roofline(agg, passes=passes)
         pct = lambda q: wall[min(len(wall) - 1, int(q * len(wall)))]
         audio_s = T / 25.0
         lines.append({
@@ -644,8 +691,8 @@ def bench_latency(args, pipe, dev):
                         "min": round(wall[0], 3), "requests": len(wall)},
             "rtf_p50": round(B * audio_s / (pct(0.50) * 1e-3), 1),
             "graph_device_ms_p50": round(dev_ms[len(dev_ms) // 2], 3),
-            "kernel_launches_in_graph": launches, "sum_of_kernel_ms": round(ksum, 3),
-            "launch_bound_gap_ms": round(dev_ms[len(dev_ms) // 2] - ksum, 3),
+            "kernel_launches_in_graph": launches, "sum_of_kernel_ms": round(ksum, 3) if ksum is not None else None,
+            "launch_bound_gap_ms": round(dev_ms[len(dev_ms) // 2] - ksum, 3) if ksum is not None else None,
             "h2d_bytes": u8_cpu.numel() + spk_cpu.numel() * 4, "d2h_bytes": out["pcm"].numel() * 2 + out["tokens"].numel() * 4,
             "top_kernels": top[:5], "dominant_kernel": roofline})
     first = lines[0]
@@ -658,7 +705,7 @@ def bench_latency(args, pipe, dev):
                                "inference_server.py:250), batch %d, hipGraph replay, uint8 frames in -> int16 PCM + unit ids out, "
                                "transfers inside the timed region" % B,
                    "clips_per_request": B, "hipgraph": True, "enc_layers": args.enc_layers, "conf_layers": args.conf_layers},
-        "roofline": first["dominant_kernel"], "cpu_baseline": None, "latency": lines}), flush=True)
+        "roofline": first["dominant_kernel"], "cpu_baseline": None, "latency": lines, "full": args.full}), flush=True)
 
 
 def dominant_roofline(agg, passes, launches_scale=1, clips_per_launch=None, frames=100):
@@ -844,8 +891,19 @@ def main():
                     help="per-request latency at --batch clips per request (use --batch 1: the reference decodes one clip per forward): "
                          "p50 / p95 wall ms incl. PCIe, graph device time, launches, sum of kernel times; 4-s and 10-s clips")
     ap.add_argument("--requests", type=int, default=200, help="timed requests of --latency")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check what the headline figure does not need: the transfer-inclusive region, the "
+                         "roofline / top-kernel pass, the CPU baseline and the parity sample against the oracle (and, with "
+                         "--latency, the per-kernel pass).  Off by default: a plain run sets up, warms up, times --steps steps "
+                         "and prints the result line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed as DIR/<name>.npy (float32, integer "
+                         "outputs as float64; at most 64 MB in all: outputs too large for that are dumped for a fixed, seeded "
+                         "sample of clips).  Rank 0's outputs")
     ap.add_argument("--stub", action="store_true", help=argparse.SUPPRESS)   # CPU rehearsal of launcher + harness (tests)
     args = ap.parse_args()
+    if args.dump_outputs and args.latency:
+        raise SystemExit("--dump-outputs is not supported with --latency")
 
     # N > 1 and no rendezvous environment: become the launcher.  Nothing above or in this branch touches the GPU.
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -903,24 +961,29 @@ def main():
         graph.replay()
         torch.cuda.synchronize()
 
+    last = {"out": out}          # what the last step computed (a replayed graph rewrites `out` in place)
+
     def step_core():
         if graph is not None:
             graph.replay()
         else:
-            step()
+            last["out"] = step()
         if world > 1:  # batch collation: ONE padded all_gather of the unit ids per batch (RCCL over xGMI), static shapes
             l2s_dist.gather_padded(out["tokens"], out["lens"] * 2, static_shape=True)
 
     step_core()
     elapsed = timed_region(step_core, args.steps, torch.cuda.synchronize, dev)
     per_rank = PER_RANK["ms_per_step"]
+    dumped = None
+    if rank == 0 and args.dump_outputs:
+        dumped = dump_outputs(args.dump_outputs, last["out"])
 
     audio_s = world * B * (T / 25.0) * args.steps
     rtf = audio_s / elapsed
     ms_per_step = 1e3 * elapsed / args.steps
 
     xfer = None
-    if use_u8 and not args.no_transfers:
+    if args.full and use_u8 and not args.no_transfers:
         el2, h2d_bytes, d2h_bytes, distinct = transfer_inclusive(args, step_core, frames_dev, out, u8_cpu, args.steps, dev)
         xfer = {"value": round(audio_s / el2, 2), "unit": "audio-sec/wall-sec", "ms_per_step": round(1e3 * el2 / args.steps, 3),
                 "vs_device_only": round(el2 / elapsed, 4), "h2d_bytes_per_step": h2d_bytes, "d2h_bytes_per_step": d2h_bytes,
@@ -932,7 +995,7 @@ def main():
     # ---- roofline of the dominant kernel: per-launch HIP events on the launch stream, eager pass ----
     roofline = None
     top = []
-    if rank == 0:
+    if rank == 0 and args.full:
         prof = ops.KernelProfiler()
         ops.set_profiler(prof)
         bl = B // nstreams                                   # clips per launch
@@ -946,7 +1009,7 @@ def main():
                                           frames=T)
 
     cpu = parity = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline:
         torch.cuda.synchronize()
         n_cpu = min(B, args.cpu_warm + args.cpu_clips)
         host = {k: out[k][:n_cpu].float().cpu() if k != "tokens" else out[k][:n_cpu].cpu()
@@ -980,7 +1043,8 @@ def main():
             "roofline": roofline, "cpu_baseline": cpu,
             "whole_step": {"tflops": round(step_tflops, 1), "frac_of_mfma_peak": round(step_tflops / PEAK_MFMA_TFLOPS, 4),
                            "gflop_per_clip": GFLOP_PER_4S_CLIP} if step_tflops else None,
-            "transfer_inclusive": xfer, "parity_vs_oracle": parity, "top_kernels": top,
+            "transfer_inclusive": xfer, "parity_vs_oracle": parity, "top_kernels": top, "full": args.full,
+            "dumped_outputs": dumped,
         }
         print(json.dumps(line), flush=True)
     if world > 1:

@@ -66,3 +66,23 @@ def test_mixed_frame_budget_buckets_are_the_same_on_every_rank():
             assert all(len(b) * max(b) <= 4000 for b in buckets[:-1])
         assert sorted(x for pr in per_rank for x in pr[1]) == sorted(int(v) for v in per_rank[0][0])
     assert [len(b) for b in bench.mixed_buckets(40, 16, 0, 1, 4000)[2]] == [16, 16, 8]      # --bucket N: fixed clip counts
+
+
+def test_dump_outputs_fits_budget_with_a_seeded_clip_sample(tmp_path):
+    """bench.dump_outputs (--dump-outputs): small outputs whole, large ones for the same seeded clips in every output and every
+    call, float32 / exact float64 files, all files within the byte budget."""
+    import numpy as np
+    import torch
+    import bench
+    arrays = {"wav": torch.randn(64, 10000, generator=torch.Generator().manual_seed(1)).half(),
+              "tokens": torch.arange(64 * 9, dtype=torch.int32).view(64, 9), "lens": torch.full((64,), 9, dtype=torch.int32)}
+    info = [bench.dump_outputs(str(tmp_path / str(i)), arrays, budget=1 << 20) for i in range(2)]
+    assert info[0]["files"] == info[1]["files"] == ["lens.npy", "tokens.npy", "wav.npy"] and info[0]["bytes"] <= 1 << 20
+    assert info[0]["sampled"] == ["wav"] and info[0]["sample_clips"] == info[1]["sample_clips"]
+    pick = info[0]["sample_clips"]
+    assert 1 <= len(pick) < 64 and pick == sorted(set(pick))
+    wav = np.load(tmp_path / "0" / "wav.npy")
+    assert wav.dtype == np.float32 and np.array_equal(wav, arrays["wav"].float().numpy()[pick])
+    tok = np.load(tmp_path / "0" / "tokens.npy")
+    assert tok.dtype == np.float64 and np.array_equal(tok, arrays["tokens"].numpy())
+    assert sum(f.stat().st_size for f in (tmp_path / "0").iterdir()) <= (1 << 20) + 3 * 256     # + .npy headers
