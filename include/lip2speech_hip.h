@@ -27,7 +27,7 @@
 extern "C" {
 #endif
 
-#define L2S_ABI_VERSION 14
+#define L2S_ABI_VERSION 15
 
 /* element type of 16-bit operands */
 enum { L2S_F16 = 0, L2S_BF16 = 1 };
@@ -225,6 +225,34 @@ int l2s_beam_decode(const float* logits, int ldl, const int32_t* lens, int len_m
                     float lenpen, int beam, void* workspace, size_t workspace_bytes, int32_t* tokens, float* pos_scores,
                     float* score, int32_t* nhyp, void* stream);
 size_t l2s_beam_decode_workspace(int B, int T2, int beam);
+
+/*
+ * CTC text head outputs (TEXT_SUPERVISION=1, multi_target_lip2speech/sequence_generator.py:141-171), per frame t < lens[b]*len_mul
+ * of logits [B*L, ldl] fp32 (V classes, blank = 0): p = softmax in fp32, labels[b, t] = argmax p (ties: first index; 0 on
+ * padded frames); topk_cls / topk_lp [B, L, K]: the K most probable classes, p descending (ties: smaller index), with
+ * log(p + FLT_MIN) (ctcdecode get_pruned_log_probs); padded frames hold class 0 / -FLT_MAX.  K = 0 writes labels only.
+ * V <= 4096, K <= 64, K <= V.
+ */
+int l2s_ctc_frames(const float* logits, int ldl, const int32_t* lens, int len_mul, int B, int L, int V, int K, int32_t* labels,
+                   int32_t* topk_cls, float* topk_lp, void* stream);
+
+/*
+ * CTC prefix beam search over l2s_ctc_frames' top-K (ctcdecode CTCBeamDecoder without a language model: DecoderState::next /
+ * PathTrie, alpha = beta = 0, cutoff_prob = 1), one workgroup per clip over its lens[b]*len_mul frames.  beam <= 64, K <= 64,
+ * nbest <= beam.  labels [B, nbest, L] int32 (collapsed label ids, 0 behind the length), lengths [B, nbest], scores [B, nbest] =
+ * -(log probability of the prefix), best first; a beam that does not exist has length 0 and score FLT_MAX.
+ * workspace: l2s_ctc_beam_workspace(B, L, beam) bytes (8-byte aligned); 0 from the query = unsupported size.
+ */
+int l2s_ctc_beam_search(const int32_t* topk_cls, const float* topk_lp, const int32_t* lens, int len_mul, int B, int L, int K,
+                        int beam, int nbest, void* workspace, size_t workspace_bytes, int32_t* labels, int32_t* lengths,
+                        float* scores, void* stream);
+size_t l2s_ctc_beam_workspace(int B, int L, int beam);
+/*
+ * REPEAT_TEXT_LABELS forward fill of framewise labels (multi_input_vocoder/dataset_multi_input.py:23-38): y[b, t] = x[b, j] for
+ * the last j <= t with x[b, j] != 0, else 0; frames t >= lens[b]*len_mul get 0.  x [B, ldx], y [B, ldy] int32; y == x allowed.
+ */
+int l2s_ctc_repeat_labels(const int32_t* x, int ldx, const int32_t* lens, int len_mul, int B, int L, int32_t* y, int ldy,
+                          void* stream);
 
 /* time-major frame duplication x2 (sequence_generator.py:130-131) fused with a cast: x:[B*T, C] fp32 -> y:[B*2T, C] 16-bit */
 int l2s_repeat2_cast(const float* x, void* y, int B, int T, int C, int dtype, void* stream);

@@ -13,7 +13,7 @@ F16, BF16 = 0, 1
 ACT_NONE, ACT_RELU, ACT_GELU, ACT_SWISH, ACT_PRELU, ACT_LRELU, ACT_TANH = range(7)
 F_RES_PRE, F_RES_POST, F_ACCUM, F_DUAL, F_MASK, F_OUT_F32, F_RES_F32 = (1 << i for i in range(7))
 MODE_LINEAR, MODE_CONV1D, MODE_CONV2D = 0, 1, 2
-ABI_VERSION = 14
+ABI_VERSION = 15
 
 _ERR = {-1: "L2S_EINVAL", -2: "L2S_ESHAPE", -3: "L2S_EALIGN", -4: "L2S_EUNSUPPORTED"}
 
@@ -80,6 +80,10 @@ SIGNATURES = {
     "l2s_greedy_decode": ([_vp, _i, _vp, _i, _i, _i, _i, _f, _f, _vp, _vp, _vp, _vp], _i),
     "l2s_beam_decode": ([_vp, _i, _vp, _i, _i, _i, _i, _f, _f, _i, _vp, ctypes.c_size_t, _vp, _vp, _vp, _vp, _vp], _i),
     "l2s_beam_decode_workspace": ([_i, _i, _i], ctypes.c_size_t),
+    "l2s_ctc_frames": ([_vp, _i, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp], _i),
+    "l2s_ctc_beam_search": ([_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, ctypes.c_size_t, _vp, _vp, _vp, _vp], _i),
+    "l2s_ctc_beam_workspace": ([_i, _i, _i], ctypes.c_size_t),
+    "l2s_ctc_repeat_labels": ([_vp, _i, _vp, _i, _i, _i, _vp, _i, _vp], _i),
     "l2s_repeat2_cast": ([_vp, _vp, _i, _i, _i, _i, _vp], _i),
     "l2s_splitk_reduce": ([_vp, _i, _i, _vp, _i, _i, _i, _vp], _i),
     "l2s_splitk_reduce_layernorm": ([_vp, _i, _i, _vp, _i, _vp, _vp, _f, _vp, _i, _i, _i, _i, _vp, _i, _i, _i, _vp], _i),

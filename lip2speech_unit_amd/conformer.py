@@ -8,7 +8,8 @@ computes for each clip alone (it runs batch_size=1, inference.py:161): padded ke
 beyond a clip's length are zeroed before every temporal conv (depthwise k=31, mel_conv k=3).
 """
 import math
-from dataclasses import dataclass
+import os
+from dataclasses import dataclass, field
 
 import torch
 import torch.nn as nn
@@ -29,6 +30,10 @@ class ConformerConfig:
     decoder_embed_dim: int = 204    # len(tgt_dict), model_avhubert.py:112
     spk_dim: int = 256
     mel_dim: int = 160
+    # CTC text head (model_avhubert.py:208-211,294-295); the reference's dataclass default is the env switch (model.py:43).
+    # text_classes is a starting size only: a checkpoint's conformer.text_classifier.classifier.weight sets the real one
+    text_supervision: bool = field(default_factory=lambda: bool(int(os.environ.get("TEXT_SUPERVISION", 0))))
+    text_classes: int = 4000        # sentencepiece lrs2lrs3_lower.vocab (helpers.py:8,20; 39 with CHAR_LEVEL=1)
 
     @classmethod
     def from_model_cfg(cls, cfg):
@@ -39,7 +44,23 @@ class ConformerConfig:
         c = cls()
         for k in ("conformer_embed_dim", "conformer_attention_heads", "conformer_ffn_embed_dim", "conformer_layers"):
             setattr(c, k, int(cfg_get(cfg, k, getattr(c, k))))
+        c.text_supervision = bool(cfg_get(cfg, "text_supervision", c.text_supervision))
         return c
+
+
+class TextClassifier(nn.Module):
+    """model.py:307-315: Linear(d, V_text) on the conformer output after after_norm.  V_text follows the checkpoint: loading a
+    classifier.weight of another row count resizes the Linear first (the product needs no sentencepiece model)."""
+
+    def __init__(self, d, num_classes):
+        super().__init__()
+        self.classifier = nn.Linear(d, num_classes)
+
+    def _load_from_state_dict(self, state_dict, prefix, *a, **k):
+        w = state_dict.get(prefix + "classifier.weight")
+        if w is not None and w.dim() == 2 and w.shape[0] != self.classifier.out_features and w.shape[1] == self.classifier.in_features:
+            self.classifier = nn.Linear(w.shape[1], w.shape[0])    # children load after this hook
+        super()._load_from_state_dict(state_dict, prefix, *a, **k)
 
 
 class PositionwiseFeedForward(nn.Module):
@@ -296,6 +317,7 @@ class Conformer(nn.Module):
             nn.Conv1d(d, d, 3, 1, 1), nn.Dropout(0.0), nn.GELU(),
             nn.Conv1d(d, d, 3, 1, 1), nn.Dropout(0.0), nn.GELU())
         self.mel_proj = nn.Linear(d, cfg.mel_dim)
+        self.text_classifier = TextClassifier(d, cfg.text_classes) if cfg.text_supervision else None
         self.dtype = dtype
         self._packed = None
 
@@ -337,6 +359,17 @@ class Conformer(nn.Module):
         P["w_mel"], P["b_mel"] = w16(self.mel_proj.weight.detach()[perm]), _f32(self.mel_proj.bias.detach()[perm], dev)
         if self.proj_out is not None:
             P["w_out"], P["b_out"] = w16(self.proj_out.weight), _f32(self.proj_out.bias, dev)
+        if self.text_classifier is not None:
+            # rows padded to a multiple of 4 (the tap-GEMM's N rule) with zero weights and a -FLT_MAX bias: a padded class
+            # never wins, and the decode reads the first V columns only
+            lin = self.text_classifier.classifier
+            V = lin.out_features
+            Vp = -(-V // 4) * 4
+            w = torch.zeros(Vp, lin.in_features)
+            w[:V] = lin.weight.detach().float().cpu()
+            b = torch.full((Vp,), -torch.finfo(torch.float32).max)
+            b[:V] = lin.bias.detach().float().cpu()
+            P["w_text"], P["b_text"], P["v_text"] = w16(w), b.to(dev).contiguous(), V
         P["dev_probe"] = P["b_mel"]
         self._packed = P
 
@@ -384,6 +417,24 @@ class Conformer(nn.Module):
             logits = None
         return logits, mel, y16
 
+    @property
+    def text_classes(self):
+        return self.text_classifier.classifier.out_features if self.text_classifier is not None else 0
+
+    def text_rows(self, y16):
+        """The CTC text head (model_avhubert.py:294-295) on forward_rows' y16 [M, d]: fp32 logits [M, Vp] in one tap-GEMM
+        launch; columns >= text_classes are padding (-FLT_MAX)."""
+        if self.text_classifier is None:
+            raise RuntimeError("this conformer has no text head (TEXT_SUPERVISION=0)")
+        dev = y16.device
+        if self._packed is None or self._packed["dev_probe"].device != dev:
+            self.pack(dev)
+        P, d = self._packed, self.cfg.conformer_embed_dim
+        M, Vp = y16.shape[0], P["w_text"].shape[0]
+        out = torch.empty(M, Vp, device=dev, dtype=torch.float32)
+        ops.tapgemm(y16, P["w_text"], out, M=M, N=Vp, Cin=d, bias=P["b_text"], dtype=self.dtype)
+        return out
+
     def forward(self, source, padding_mask, spk_emb=None, tbc=True, **kwargs):
         """model_avhubert.py:249-297: source [2T,B,1024] (tbc) or [B,2T,1024]; padding_mask [B,2T] bool."""
         x = source.transpose(0, 1) if tbc else source
@@ -394,12 +445,16 @@ class Conformer(nn.Module):
         lens = ops.lens_from_mask(None if padding_mask is None else padding_mask.to(torch.bool).contiguous(), B, T, dev)
         if spk_emb is None:
             raise NotImplementedError("the mel head of the released checkpoints is built with the 256-d speaker embedding")
-        logits, mel, _ = self.forward_rows(src16, lens, B, T, spk_emb, len_mul=1)
+        logits, mel, y16 = self.forward_rows(src16, lens, B, T, spk_emb, len_mul=1)
         V = logits.shape[1]
         unit = logits.view(B, T, V)
         unit = unit.transpose(0, 1) if tbc else unit
-        return {"encoder_out": unit, "encoder_padding_mask": padding_mask, "padding_mask": padding_mask,
-                "encoder_out_mel": mel.view(B, 2 * T, self.cfg.mel_dim // 2)}
+        out = {"encoder_out": unit, "encoder_padding_mask": padding_mask, "padding_mask": padding_mask,
+               "encoder_out_mel": mel.view(B, 2 * T, self.cfg.mel_dim // 2)}
+        if self.text_classifier is not None:                                             # :294-295, T x B x V like encoder_out
+            text = self.text_rows(y16)[:, : self.text_classes].reshape(B, T, -1)
+            out["encoder_out_text"] = text.transpose(0, 1) if tbc else text
+        return out
 
     def reorder_encoder_out(self, encoder_out, new_order):
         if encoder_out["encoder_out"] is not None:

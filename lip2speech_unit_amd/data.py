@@ -142,10 +142,26 @@ class MultiTargetDataset(DatasetBase):
 
 
 # ---- stage 2 -----------------------------------------------------------------------------------------------------
+def repeat_text_labels(labels):
+    """dataset_multi_input.py:23-38 `repeat`: CTC blanks (0) and label changes forward-filled from the first label."""
+    out, cur = [labels[0]], labels[0]
+    for x in labels[1:]:
+        if x != 0 and x != cur:
+            cur = x
+        out.append(cur)
+    return out
+
+
 def parse_manifest(manifest_path, max_keep=None, min_keep=None):
-    """dataset_multi_input.py:41-110: returns (audio_files, mel_files, codes)."""
-    audio_files, mels, codes = [], [], []
+    """dataset_multi_input.py:41-110: returns (audio_files, mel_files, codes), plus t_labels (lists of int) when
+    TEXT_SUPERVISION=1 and the label file <manifest>.txt exists: one line per KEPT utterance (the reference reads a line only
+    for rows it keeps), forward-filled under REPEAT_TEXT_LABELS=1."""
+    audio_files, mels, codes, t_labels = [], [], [], []
     code_path = os.path.splitext(manifest_path)[0] + ".unt"
+    t_path = os.path.splitext(manifest_path)[0] + ".txt"
+    text = bool(int(os.environ.get("TEXT_SUPERVISION", 0))) and os.path.exists(t_path)
+    rep = text and bool(int(os.environ.get("REPEAT_TEXT_LABELS", 0)))
+    f_t = open(t_path) if text else None
     with open(manifest_path) as f, open(code_path) as f_c:
         root = f.readline().strip()
         for line, line_code in zip(f, f_c):
@@ -160,7 +176,13 @@ def parse_manifest(manifest_path, max_keep=None, min_keep=None):
             audio_files.append(audio_path)
             mels.append(audio_path.replace("/audio/", "/mel/")[:-4] + ".npy")
             codes.append(code)
-    return audio_files, mels, codes
+            if text:
+                t = [int(x) for x in f_t.readline().strip().split(" ")]
+                t_labels.append(repeat_text_labels(t) if rep else t)
+    if not text:
+        return audio_files, mels, codes
+    f_t.close()
+    return audio_files, mels, codes, t_labels
 
 
 def load_code_dict(path):
@@ -195,7 +217,8 @@ def audio_num_samples(path, pad=None):
 
 class MelCodeDataset:
     def __init__(self, file_list, code_hop_size=320, mel_hop_size=160, code_dict_path=None, pad=None):
-        self.audio_files, self.mel_files, self.codes = file_list
+        self.audio_files, self.mel_files, self.codes = file_list[:3]
+        self.t_labels = file_list[3] if len(file_list) > 3 else None   # text supervision (dataset_multi_input.py:225-239)
         self.code_hop_size, self.mel_hop_size, self.pad = code_hop_size, mel_hop_size, pad
         self.code_dict = load_code_dict(code_dict_path)
         self.speaker_emb_files = [f.replace("/audio/", "/spk_emb/")[:-4] + ".npy" for f in self.audio_files]
@@ -204,12 +227,16 @@ class MelCodeDataset:
         return len(self.audio_files)
 
     def __getitem__(self, index):
-        """dataset_multi_input.py:198-291 with segment_size=-1: (feats{code,mel,spkr}, None, filename, None)."""
+        """dataset_multi_input.py:198-291 with segment_size=-1: (feats{code,mel,spkr[,t_label]}, None, filename, None)."""
         filename = self.audio_files[index]
         n_audio = audio_num_samples(filename, self.pad)
         code = np.array(code_to_sequence(self.codes[index].split(), self.code_dict))
         code_length = min(n_audio // self.code_hop_size, code.shape[0])
         code = code[:code_length]
+        t_label = None
+        if self.t_labels is not None:
+            t_label = np.asarray(self.t_labels[index], dtype=np.int64)[:code_length]
+            assert t_label.shape[0] == code.shape[0], f"{filename}: {t_label.shape[0]} != {code.shape[0]}"
         mel = np.load(self.mel_files[index])
         mel_length = min(n_audio // self.mel_hop_size, mel.shape[0])
         mel = mel[:mel_length]
@@ -220,4 +247,6 @@ class MelCodeDataset:
         assert cut // self.mel_hop_size == mel.shape[0], "Mel audio mismatch"
         feats = {"code": code.astype(np.int64), "mel": np.ascontiguousarray(mel.transpose(1, 0)).astype(np.float32),
                  "spkr": np.load(self.speaker_emb_files[index]).astype(np.float32)}
+        if t_label is not None:
+            feats["t_label"] = t_label[: cut // self.code_hop_size]
         return feats, None, str(filename), None

@@ -174,7 +174,7 @@ def build_vocoder(cfg):
     (`vocoder.checkpoint`; "synthetic[:seed]" accepted), weight norm removed, on the GPU."""
     from .vocoder import AttrDict, MelCodeGenerator
     h = AttrDict(json.load(open(cfg["vocoder.config"])))
-    h.text_supervision = False
+    h.text_supervision = bool(int(os.environ.get("TEXT_SUPERVISION", 0)))   # multi_input_vocoder/inference.py:112
     voc = MelCodeGenerator(h, dtype=ops.BF16 if cfg["dtype"] == "bf16" else ops.F16)
     path = cfg["vocoder.checkpoint"]
     if path is None or str(path).startswith("synthetic"):
@@ -234,7 +234,16 @@ def decode_dataset(cfg, task, model, ds, results_path, logger, rank=0, world=1, 
                                 for h in hypos])
             code = (toks - 4).clamp_(min=0)
             mel = generator.last_mel.transpose(1, 2).contiguous()
-            _, pcm = vocoder.forward_rows(code, mel, ni["spk_emb"], batch["target_lengths"].to(torch.int32))
+            t_label = None
+            if getattr(vocoder, "text_supervision", False):
+                # the framewise labels whatever the decode mode (create_dataset.py:402-425 reads pred_text's first line)
+                t_label = getattr(generator, "last_text", None)
+                if int(os.environ.get("REPEAT_TEXT_LABELS", 0)):
+                    filled = torch.empty_like(t_label)
+                    ops.ctc_repeat_labels(t_label, filled, B=t_label.shape[0], L=t_label.shape[1],
+                                          lens=batch["target_lengths"].to(torch.int32), len_mul=1)
+                    t_label = filled
+            _, pcm = vocoder.forward_rows(code, mel, ni["spk_emb"], batch["target_lengths"].to(torch.int32), t_label=t_label)
             pcm = pcm.cpu().numpy()
         if dev.type == "cuda":
             torch.cuda.synchronize()
@@ -253,6 +262,12 @@ def decode_dataset(cfg, task, model, ds, results_path, logger, rank=0, world=1, 
             os.makedirs(os.path.dirname(unit_path), exist_ok=True)
             with open(unit_path, "w") as f:
                 f.write(hypo_str)
+            if "pred_text_labels" in batch:                                          # :276-284 (TEXT_SUPERVISION=1)
+                text_path = os.path.join(results_path, "pred_text", utt + ".txt")
+                os.makedirs(os.path.dirname(text_path), exist_ok=True)
+                with open(text_path, "w") as f:
+                    for labels in batch["pred_text_labels"][i]:
+                        f.write(" ".join(str(x) for x in labels) + "\n")
             if pcm is not None:
                 from scipy.io.wavfile import write as write_wav
                 wav_path = os.path.join(results_path, "pred_wav", *utt.split("/")[-2:]) + ".wav"

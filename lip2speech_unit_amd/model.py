@@ -114,6 +114,7 @@ class Conformer(_ConformerHead):
     def __init__(self, cfg: ConformerConfig = None, dtype=ops.F16):
         cfg = cfg or ConformerConfig()
         cfg.encoder_embed_dim = cfg.conformer_embed_dim      # 512 != d never holds: proj_in is None (:216-219)
+        cfg.text_supervision = False                         # the reference's model.py Conformer has no text head
         super().__init__(cfg, dtype=dtype)
         self.encoder.frontend = Conv3dResNet(relu_type="swish", dtype=dtype)
 

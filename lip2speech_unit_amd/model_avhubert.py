@@ -20,7 +20,8 @@ from .plugin import ModelBase, cfg_get, register_model
 #  * the audio sub-model is never reached with modalities=['video'] (conf/decode.yaml:23);
 #  * pre-training heads are dropped by remove_pretraining_modules() (:108); BatchNorm's num_batches_tracked is bookkeeping;
 #  * `multi_target` checkpoints keep the (unused) ESPnet frontend under conformer.encoder.frontend;
-#  * text-supervision heads (TEXT_SUPERVISION=1, model_avhubert.py:208-229) are outside the inference path.
+#  * text-supervision heads (conformer.text_*, model_avhubert.py:208-229) load as parameters when the conformer is built
+#    with its text head (TEXT_SUPERVISION=1) and are ignored otherwise.
 ALLOWED_MISSING = ("encoder.w2v_model.mask_emb", "encoder.w2v_model.feature_extractor_audio.")
 ALLOWED_UNEXPECTED = ("encoder.w2v_model.final_proj", "encoder.w2v_model.label_embs_concat", "encoder.w2v_model.mask_emb",
                       "num_batches_tracked", "conformer.encoder.frontend.", "conformer.ctc", "conformer.text_",

@@ -239,6 +239,60 @@ def beam_decode(logits, *, B, T2, V, beam, ldl=None, lens=None, len_mul=1, tempe
     return tokens, pos, score, nhyp
 
 
+def ctc_frames(logits, labels, topk_cls, topk_lp, *, B, L, V, K, ldl=None, lens=None, len_mul=1):
+    """CTC text head outputs per frame (fp32 softmax of logits [B*L, ldl]): labels int32 [B, L] = framewise argmax, and with
+    K > 0 the top-K classes topk_cls int32 / topk_lp fp32 [B, L, K] (log(p + FLT_MIN), p descending)."""
+    ldl = ldl if ldl is not None else V
+    _run("l2s_ctc_frames", lambda: _lib.load().l2s_ctc_frames(
+        _ptr(_req(logits, torch.float32, "logits")), ldl, _ptr(lens), len_mul, B, L, V, K, _ptr(_req(labels, torch.int32, "labels")),
+        _ptr(topk_cls), _ptr(topk_lp), _stream()))
+
+
+def ctc_beam_search(topk_cls, topk_lp, workspace, labels, lengths, scores, *, B, L, K, beam, nbest, lens=None, len_mul=1):
+    """CTC prefix beam search (ctcdecode without LM) over ctc_frames' top-K: labels int32 [B, nbest, L], lengths int32
+    [B, nbest], scores fp32 [B, nbest] (-log p of the prefix, best first).  workspace: ctc_beam_workspace(B, L, beam) bytes."""
+    _run("l2s_ctc_beam_search", lambda: _lib.load().l2s_ctc_beam_search(
+        _ptr(_req(topk_cls, torch.int32, "topk_cls")), _ptr(_req(topk_lp, torch.float32, "topk_lp")), _ptr(lens), len_mul, B, L, K,
+        beam, nbest, _ptr(workspace), workspace.numel() * workspace.element_size(), _ptr(_req(labels, torch.int32, "labels")),
+        _ptr(_req(lengths, torch.int32, "lengths")), _ptr(_req(scores, torch.float32, "scores")), _stream()))
+
+
+def ctc_repeat_labels(x, y, *, B, L, ldx=None, ldy=None, lens=None, len_mul=1):
+    """REPEAT_TEXT_LABELS: y[b, t] = the last non-zero label of x[b, :t+1] (0 if none; 0 past lens[b]*len_mul).  int32."""
+    _run("l2s_ctc_repeat_labels", lambda: _lib.load().l2s_ctc_repeat_labels(
+        _ptr(_req(x, torch.int32, "x")), ldx or x.stride(0), _ptr(lens), len_mul, B, L, _ptr(_req(y, torch.int32, "y")),
+        ldy or y.stride(0), _stream()))
+
+
+def ctc_beam_workspace_bytes(B, L, beam):
+    n = _lib.load().l2s_ctc_beam_workspace(B, L, beam)
+    if n == 0:
+        raise L2SError(f"l2s_ctc_beam_workspace: unsupported size (B={B}, L={L}, beam={beam})")
+    return n
+
+
+def ctc_decode(logits, *, B, L, V, ldl=None, lens=None, len_mul=1, beam=0, K=40, nbest=3):
+    """Text decode of the CTC head, all on the device (no host sync: capturable).  Returns {"text": int32 [B, L] framewise
+    argmax} and, with beam > 0 (CTC_BS_DECODING=1: beam 30, cutoff_top_n 40, top 3), "text_beams" int32 [B, nbest, L],
+    "text_lens" int32 [B, nbest], "text_scores" fp32 [B, nbest]."""
+    dev = logits.device
+    labels = torch.empty(B, L, device=dev, dtype=torch.int32)
+    if beam <= 0:
+        ctc_frames(logits, labels, None, None, B=B, L=L, V=V, K=0, ldl=ldl, lens=lens, len_mul=len_mul)
+        return {"text": labels}
+    K = min(K, V)
+    nbest = min(nbest, beam)
+    tc = torch.empty(B, L, K, device=dev, dtype=torch.int32)
+    tl = torch.empty(B, L, K, device=dev, dtype=torch.float32)
+    ctc_frames(logits, labels, tc, tl, B=B, L=L, V=V, K=K, ldl=ldl, lens=lens, len_mul=len_mul)
+    work = torch.empty(ctc_beam_workspace_bytes(B, L, beam) // 8, device=dev, dtype=torch.int64)
+    beams = torch.empty(B, nbest, L, device=dev, dtype=torch.int32)
+    blen = torch.empty(B, nbest, device=dev, dtype=torch.int32)
+    bsc = torch.empty(B, nbest, device=dev, dtype=torch.float32)
+    ctc_beam_search(tc, tl, work, beams, blen, bsc, B=B, L=L, K=K, beam=beam, nbest=nbest, lens=lens, len_mul=len_mul)
+    return {"text": labels, "text_beams": beams, "text_lens": blen, "text_scores": bsc}
+
+
 def repeat2_cast(x, y, B, T, C, dtype):
     _run("l2s_repeat2_cast", lambda: _lib.load().l2s_repeat2_cast(_ptr(x), _ptr(y), B, T, C, dtype, _stream()))
 
@@ -512,6 +566,12 @@ _SCHEMAS = {
     "beam_decode": "(Tensor logits, *, int B, int T2, int V, int beam, int? ldl=None, Tensor? lens=None, int len_mul=1, "
                    "float temperature=1.0, float lenpen=1.0) -> (Tensor, Tensor, Tensor, Tensor)",
     "repeat2_cast": "(Tensor x, Tensor(a!) y, int B, int T, int C, int dtype) -> ()",
+    "ctc_frames": "(Tensor logits, Tensor(a!) labels, Tensor(b!)? topk_cls, Tensor(c!)? topk_lp, *, int B, int L, int V, int K, "
+                  "int? ldl=None, Tensor? lens=None, int len_mul=1) -> ()",
+    "ctc_repeat_labels": "(Tensor x, Tensor(a!) y, *, int B, int L, int? ldx=None, int? ldy=None, Tensor? lens=None, "
+                         "int len_mul=1) -> ()",
+    "ctc_beam_search": "(Tensor topk_cls, Tensor topk_lp, Tensor(a!) workspace, Tensor(b!) labels, Tensor(c!) lengths, "
+                       "Tensor(d!) scores, *, int B, int L, int K, int beam, int nbest, Tensor? lens=None, int len_mul=1) -> ()",
     "splitk_reduce": "(Tensor P, Tensor(a!) x, *, int M, int N, int S, int? ldp=None, int? ldx=None) -> ()",
     "splitk_reduce_layernorm": "(Tensor P, Tensor(a!) x, Tensor gamma, Tensor beta, float eps, Tensor(b!) y, *, int M, int C, int S, "
                                "int? ldp=None, int? ldx=None, int? ldy=None, Tensor? lens=None, int len_mul=1, int mask_T=0, int dtype=0) -> ()",
@@ -549,7 +609,8 @@ _SCHEMAS = {
 ENTRY_OF = {n: "l2s_" + n for n in _SCHEMAS}
 ENTRY_OF.update({"maxpool2d_3x3s2": "l2s_maxpool2d_3x3s2", "avgpool_hw": "l2s_avgpool_hw"})
 # host-side queries of the ABI (no launch, nothing for the dispatcher to see)
-HOST_QUERIES = ("l2s_abi_version", "l2s_build_info", "l2s_tapgemm_variant", "l2s_tapgemm_epilogue_family", "l2s_beam_decode_workspace")
+HOST_QUERIES = ("l2s_abi_version", "l2s_build_info", "l2s_tapgemm_variant", "l2s_tapgemm_epilogue_family", "l2s_beam_decode_workspace",
+                "l2s_ctc_beam_workspace")
 # SURVEY 8(b)'s operator names -> the entry that implements them (`mel_head` is a composition of linear_epilogue launches,
 # conformer.py::Conformer.forward_rows; it has no kernel of its own)
 ALIASES = {"frontend3d_stem": "stem_pool_fused", "resnet_trunk": "basiclayer_fused", "linear_epilogue": "tapgemm",

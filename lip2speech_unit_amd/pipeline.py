@@ -54,11 +54,25 @@ class GraphCache:
         return e[2]
 
 
+def text_decode(conformer, y16, lens, B, T2, beam_search=False):
+    """CTC text head of a text-supervised conformer on its y16 rows, decoded on the device: {"text_logits", "text"} and under
+    beam_search {"text_beams", "text_lens", "text_scores"} (ops.ctc_decode)."""
+    tl = conformer.text_rows(y16)
+    Vt = conformer.text_classes
+    d = ops.ctc_decode(tl, B=B, L=T2, V=Vt, ldl=tl.shape[1], lens=lens, len_mul=2, beam=30 if beam_search else 0, K=40, nbest=3)
+    d["text_logits"] = tl.view(B, T2, -1)
+    return d
+
+
 class LipToSpeechPipeline:
     def __init__(self, model, vocoder, temperature: float = 1.0, len_penalty: float = 1.0):
         self.model, self.vocoder = model, vocoder
         self.temperature, self.len_penalty = temperature, len_penalty
         self._shared_ready = set()
+        # text-supervised checkpoints: CTC prefix beam search instead of the framewise argmax (sequence_generator.py:20-38)
+        self.ctc_beam = int(os.environ.get("CTC_BS_DECODING", "0")) != 0
+        # text-supervised vocoders: its label file forward-filled (dataset_multi_input.py:23-38, REPEAT_TEXT_LABELS=1)
+        self.repeat_text = int(os.environ.get("REPEAT_TEXT_LABELS", "0")) != 0
 
     def _shared_state_key(self, dev, T):
         """Identity of the lazily built state sub-batches share: device, frames per clip and the packed-weight object of every
@@ -69,29 +83,51 @@ class LipToSpeechPipeline:
 
     @torch.no_grad()
     def stage1_device(self, video, padding_mask, spk_emb):
-        """Returns dict of device tensors: tokens int32 [B,2T+1], lprobs, score, mel fp32 [B,4T,80], logits, lens."""
+        """Returns dict of device tensors: tokens int32 [B,2T+1], lprobs, score, mel fp32 [B,4T,80], logits, lens.  With a text
+        head (TEXT_SUPERVISION=1) also text int32 [B,2T] (framewise CTC argmax, 0 past a clip's length) and text_logits
+        fp32 [B,2T,Vp]; under CTC_BS_DECODING=1 text_beams int32 [B,3,2T], text_lens [B,3], text_scores [B,3] (the top 3 of
+        a 30-wide prefix beam search over the 40 most probable classes per frame)."""
         m = self.model
         enc_mod = m.encoder.w2v_model if hasattr(m.encoder, "w2v_model") else m.encoder   # AV-HuBERT / Auto-AVSR encoder
         enc, lens, B, T = enc_mod.extract_rows(video, padding_mask)
         dt = m.conformer.dtype
         src16 = torch.empty(B * 2 * T, enc.shape[1], device=enc.device, dtype=ops.torch_dtype(dt))
         ops.repeat2_cast(enc, src16, B, T, enc.shape[1], dt)
-        logits, mel, _ = m.conformer.forward_rows(src16, lens, B, 2 * T, spk_emb, len_mul=2)
+        logits, mel, y16 = m.conformer.forward_rows(src16, lens, B, 2 * T, spk_emb, len_mul=2)
         T2, V = 2 * T, logits.shape[1]
         tokens = torch.empty(B, T2 + 1, device=enc.device, dtype=torch.int32)
         lprobs = torch.empty(B, T2 + 1, device=enc.device, dtype=torch.float32)
         score = torch.empty(B, device=enc.device, dtype=torch.float32)
         ops.greedy_decode(logits, tokens, lprobs, score, B=B, T2=T2, V=V, lens=lens, len_mul=2,
                           temperature=self.temperature, lenpen=self.len_penalty)
-        return {"tokens": tokens, "lprobs": lprobs, "score": score, "mel": mel.view(B, 2 * T2, -1),
-                "logits": logits.view(B, T2, V), "lens": lens, "encoder_out": enc.view(B, T, -1)}
+        out = {"tokens": tokens, "lprobs": lprobs, "score": score, "mel": mel.view(B, 2 * T2, -1),
+               "logits": logits.view(B, T2, V), "lens": lens, "encoder_out": enc.view(B, T, -1)}
+        if getattr(m.conformer, "text_classifier", None) is not None:
+            out.update(text_decode(m.conformer, y16, lens, B, T2, self.ctc_beam))
+        return out
 
     @torch.no_grad()
     def stage2_device(self, s1, spk_emb):
         """units/mel of stage 1 -> (wav fp32 [B, 640*T], pcm int16).  Rows past each clip's length come out as zero."""
         # token -> unit id, mel [B,4T,80] -> the vocoder's channels-last concat columns, lens -> row masks: all inside the
         # vocoder's own launches (no torch arithmetic / layout kernels between the stages)
-        return self.vocoder.forward_tokens_rows(s1["tokens"], s1["mel"], spk_emb, s1["lens"])
+        return self.vocoder.forward_tokens_rows(s1["tokens"], s1["mel"], spk_emb, s1["lens"], t_rows=self.text_rows(s1))
+
+    def text_rows(self, s1):
+        """The frame labels a text-supervised vocoder reads: stage 1's FRAMEWISE argmax labels whatever the decode mode
+        (create_dataset.py:402-425 copies pred_text's first line, which only has the code's length for greedy output),
+        forward-filled under REPEAT_TEXT_LABELS=1.  None for a vocoder without the text branch."""
+        if not getattr(self.vocoder, "text_supervision", False):
+            return None
+        if "text" not in s1:
+            raise ValueError("the vocoder is text-supervised but the stage-1 model has no text head (TEXT_SUPERVISION)")
+        t = s1["text"]
+        if self.repeat_text:
+            B, L = t.shape
+            filled = torch.empty_like(t)
+            ops.ctc_repeat_labels(t, filled, B=B, L=L, lens=s1["lens"], len_mul=2)
+            t = filled
+        return t
 
     @torch.no_grad()
     def forward_device(self, video, padding_mask, spk_emb):
@@ -154,7 +190,9 @@ class LipToSpeechPipeline:
                 outs.append(self.forward_device_u8(frames_u8[lo:hi], pm, spk_emb[lo:hi], **kw))
         for st in self._side_streams:
             cur.wait_stream(st)
-        return {k: torch.cat([o[k] for o in outs]) for k in ("tokens", "lens", "score", "mel", "wav", "pcm")}
+        keys = ("tokens", "lens", "score", "mel", "wav", "pcm") + tuple(k for k in ("text", "text_beams", "text_lens", "text_scores")
+                                                                       if k in outs[0])
+        return {k: torch.cat([o[k] for o in outs]) for k in keys}
 
     @torch.no_grad()
     def __call__(self, video, padding_mask, spk_emb):

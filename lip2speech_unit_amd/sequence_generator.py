@@ -11,6 +11,7 @@ kernel (l2s_greedy_decode) produces it for the whole batch.  The lower-ranked hy
 reads, are materialised on request (`nbest` > 1, up to `beam_size`) by l2s_beam_decode: the reference's beam search itself
 (BeamSearch.step + finalize_hypos), one wavefront per clip, hypotheses in the reference's order (descending score).
 """
+import os
 from typing import Dict, List, Optional
 
 import torch
@@ -48,6 +49,8 @@ class MultiTargetSequenceGenerator:
         # change a clip's result
         self.use_hipgraph, self.frame_bucket = bool(use_hipgraph), max(1, int(frame_bucket))
         self._graphs = None
+        # text-supervised checkpoints (sequence_generator.py:24-38,141-171): CTC_BS_DECODING=1 = prefix beam search, top 3 beams
+        self.use_ctc_beam_search_decoding = int(os.environ.get("CTC_BS_DECODING", "0")) != 0
         if (self.pad, self.bos, self.eos, self.unk) != (1, 0, 2, 3):
             raise NotImplementedError("the decode kernel assumes fairseq's special ids bos=0,pad=1,eos=2,unk=3")
 
@@ -62,7 +65,8 @@ class MultiTargetSequenceGenerator:
     def _device_part(self, video, padding_mask, spk_emb):
         """Everything of a batch that runs on the device, with no host synchronisation (hipGraph-capturable): encoder ->
         x2 repeat -> conformer -> heads -> greedy decode.  Returns (logits [B*2T,V], mel [B*2T,160], lens [B], tokens
-        [B,2T+1], lprobs [B,2T+1], score [B])."""
+        [B,2T+1], lprobs [B,2T+1], score [B]) and, when the conformer has a text head, its decode (pipeline.text_decode)
+        as further tensors: text [B,2T] (+ text_beams, text_lens, text_scores under CTC beam search)."""
         model = self.model
         if getattr(model, "conformer", None) is None:
             # `multi_target` (model.py:66-252): the encoder IS the conformer with its Conv3dResNet frontend (:126 only)
@@ -74,14 +78,19 @@ class MultiTargetSequenceGenerator:
             dt = model.conformer.dtype
             src16 = torch.empty(B * 2 * T, enc.shape[1], device=enc.device, dtype=ops.torch_dtype(dt))
             ops.repeat2_cast(enc, src16, B, T, enc.shape[1], dt)                        # :130-131 repeat_interleave(2)
-            logits, mel, _ = model.conformer.forward_rows(src16, lens, B, 2 * T, spk_emb, len_mul=2)  # :128-134
+            logits, mel, y16 = model.conformer.forward_rows(src16, lens, B, 2 * T, spk_emb, len_mul=2)  # :128-134
         T2, V = 2 * T, logits.shape[1]
+        text = ()
+        if getattr(getattr(model, "conformer", None), "text_classifier", None) is not None:
+            from .pipeline import text_decode
+            d = text_decode(model.conformer, y16, lens, B, T2, self.use_ctc_beam_search_decoding)
+            text = tuple(d[k] for k in ("text", "text_beams", "text_lens", "text_scores") if k in d)
         tokens = torch.empty(B, T2 + 1, device=logits.device, dtype=torch.int32)
         lprobs = torch.empty(B, T2 + 1, device=logits.device, dtype=torch.float32)
         score = torch.empty(B, device=logits.device, dtype=torch.float32)
         ops.greedy_decode(logits, tokens, lprobs, score, B=B, T2=T2, V=V, lens=lens, len_mul=2,
                           temperature=self.temperature, lenpen=self.len_penalty if self.normalize_scores else 0.0)
-        return logits, mel, lens, tokens, lprobs, score
+        return (logits, mel, lens, tokens, lprobs, score) + text
 
     def _generate(self, sample, prefix_tokens: Optional[torch.Tensor] = None, constraints=None,
                   bos_token: Optional[int] = None):
@@ -106,9 +115,10 @@ class MultiTargetSequenceGenerator:
                 video = torch.nn.functional.pad(video, (0, 0, 0, 0, 0, Tp - Tv))
                 pm = torch.nn.functional.pad(pm, (0, Tp - Tv), value=True)
             outs = self._graphs(video.contiguous(), pm.contiguous(), spk_emb.contiguous())
-            logits, mel, lens, tokens, lprobs, score = (t.clone() for t in outs)   # the capture's outputs are reused next call
+            outs = tuple(t.clone() for t in outs)   # the capture's outputs are reused next call
         else:
-            logits, mel, lens, tokens, lprobs, score = self._device_part(video, padding_mask, spk_emb)
+            outs = self._device_part(video, padding_mask, spk_emb)
+        (logits, mel, lens, tokens, lprobs, score), text = outs[:6], outs[6:]
         B, T2 = tokens.shape[0], tokens.shape[1] - 1
         T, V = T2 // 2, logits.shape[1]
 
@@ -127,6 +137,16 @@ class MultiTargetSequenceGenerator:
         self.last_mel = mel.view(B, 2 * T2, -1)                                     # device copy for the fused stage-2 hand-off
         mels = self.last_mel.cpu().numpy()                                          # :136-139
         sample["mels"] = [m[: 2 * n] for m, n in zip(mels, tl)]
+        if text:
+            # :141-171 per clip: the framewise labels (one line), or the top 3 beams' collapsed labels (3 lines)
+            if len(text) == 4:
+                beams, blen = text[1].cpu(), text[2].tolist()
+                sample["pred_text_labels"] = [[beams[b, h, : blen[b][h]].tolist() for h in range(beams.shape[1])]
+                                              for b in range(B)]
+            else:
+                lab = text[0].cpu()
+                sample["pred_text_labels"] = [[lab[b, :n].tolist()] for b, n in enumerate(tl)]
+            self.last_text = text[0]                                                 # framewise labels on the device
         tokens64 = tokens.to(torch.long)
         finalized: List[List[Dict[str, torch.Tensor]]] = []
         if self.nbest > 1:

@@ -142,8 +142,6 @@ class Lip2SpeechTask(TaskBase):
     def __init__(self, cfg: Lip2SpeechConfig, dictionary: Optional[UnitDictionary] = None):
         super().__init__(cfg)
         self.fine_tuning = True          # the path only exists fine-tuned (target_dictionary, not dictionaries)
-        if cfg_get(cfg, "text_supervision", False):
-            raise NotImplementedError("TEXT_SUPERVISION=1 is outside the lip2speech inference path")
         if dictionary is None:
             dictionary = UnitDictionary.load(os.path.join(self.get_label_dir(), f"dict.{cfg.labels[0]}.txt"))
         self._dict = dictionary

@@ -129,11 +129,15 @@ class Generator(nn.Module):
         return r
 
     # ---- packing -------------------------------------------------------------------------------------------------
+    def _conv_pre_weight(self):
+        """conv_pre's effective weight [c0, Cin, 7] in the column order of the concat buffer the launches write."""
+        return self.conv_pre.effective_weight()
+
     def _pack_generator(self, dev):
         t16 = ops.torch_dtype(self.dtype)
         h = self.h
         third = 1.0 / self.num_kernels
-        P = {"pre_w": pack_conv1d(self.conv_pre.effective_weight()).to(dev, t16).contiguous(),
+        P = {"pre_w": pack_conv1d(self._conv_pre_weight()).to(dev, t16).contiguous(),
              "pre_b": self.conv_pre.bias.detach().float().to(dev).contiguous(), "stages": []}
         for i, (u, k) in enumerate(zip(h.upsample_rates, h.upsample_kernel_sizes)):
             w = self.ups[i].effective_weight()
@@ -182,7 +186,7 @@ class Generator(nn.Module):
         stage's ups and conv_post)."""
         t16 = ops.torch_dtype(self.dtype)
         h, third = self.h, 1.0 / self.num_kernels
-        P = {"pre_w": _hi_lo(pack_conv1d(self.conv_pre.effective_weight()), t16, dev),
+        P = {"pre_w": _hi_lo(pack_conv1d(self._conv_pre_weight()), t16, dev),
              "pre_b": self.conv_pre.bias.detach().float().to(dev).contiguous(), "stages": []}
         for i, (u, k) in enumerate(zip(h.upsample_rates, h.upsample_kernel_sizes)):
             w = self.ups[i].effective_weight()
@@ -402,13 +406,25 @@ class _PreciseOps:
         ops.tapgemm(a[0], w[1], out, flags=F_ACCUM, dtype=self.dt, **kw)
 
 
+class _Permute(nn.Module):
+    """CustomPermute(0, 2, 1) of models_multi_input.py:18-23 (no parameters: keeps layer_text's indices)."""
+
+    def forward(self, x):
+        return x.permute(0, 2, 1)
+
+
+def _pad8(n):
+    return -(-n // 8) * 8
+
+
 class MelCodeGenerator(Generator):
-    """multi_input_vocoder/models_multi_input.py:26-97 (text_supervision branch not built)."""
+    """multi_input_vocoder/models_multi_input.py:26-97, with the text-supervision branch (`layer_text`, :46-56,75-77) when
+    h.text_supervision is set.  Its frame labels (one per code frame) become E_t more generator input columns between the
+    code and the speaker columns: mel 80 | code E | text E_t | spkr E.  On the device E_t is padded to a multiple of 8 with
+    zero weights (zero columns of the concat buffer, zero input columns of conv_pre)."""
 
     def __init__(self, h, dtype=ops.F16):
         super().__init__(h, dtype=dtype)
-        if h.get("text_supervision", False):
-            raise NotImplementedError("TEXT_SUPERVISION=1 vocoder branch is outside the lip2speech inference path")
         E = h.embedding_dim
         self.dict = nn.Embedding(h.num_embeddings, E)
         self.multispkr = h.get("multispkr", None)
@@ -419,6 +435,47 @@ class MelCodeGenerator(Generator):
         self.layer = nn.Sequential(nn.ConvTranspose1d(E, E, kernel_size=4, stride=2, padding=1), nn.GELU())
         self.fc = nn.Linear(E, E)
         self.num_mels = h.get("num_mels", 80)
+        self.text_supervision = bool(h.get("text_supervision", False))
+        if self.text_supervision:
+            Et = int(h.embedding_dim_text)
+            cin = self.conv_pre.weight_v.shape[1] if hasattr(self.conv_pre, "weight_v") else self.conv_pre.weight.shape[1]
+            want = self.num_mels + 2 * E + Et
+            if cin != want:
+                raise ValueError(f"text-supervised vocoder: model_in_dim = {cin}, but mel {self.num_mels} + code {E} + text {Et} "
+                                 f"+ speaker {E} = {want} (models_multi_input.py:72-82)")
+            self.layer_text = nn.Sequential(                                              # :46-56
+                nn.Embedding(int(h.num_embeddings_text), Et), _Permute(),
+                nn.ConvTranspose1d(Et, Et, kernel_size=4, stride=2, padding=1), nn.GELU(), _Permute(), nn.Dropout(0.1),
+                nn.Linear(Et, Et), _Permute())
+
+    def _text_dims(self):
+        Et = self.layer_text[0].embedding_dim
+        return Et, _pad8(Et)
+
+    def _conv_pre_weight(self):
+        w = self.conv_pre.effective_weight()
+        if not self.text_supervision:
+            return w
+        Et, Etp = self._text_dims()
+        c = self.num_mels + self.h.embedding_dim + Et
+        return torch.cat([w[:, :c], w.new_zeros(w.shape[0], Etp - Et, w.shape[2]), w[:, c:]], 1)
+
+    def _text_weights(self):
+        """layer_text's weights in fp32, padded to E_t' = a multiple of 8: table [V, E_t'], ConvTranspose [E_t', E_t', 4] + bias,
+        Linear [E_t', E_t'] + bias."""
+        Et, Etp = self._text_dims()
+        emb, ct, fc = self.layer_text[0], self.layer_text[2], self.layer_text[6]
+        table = torch.zeros(emb.num_embeddings, Etp)
+        table[:, :Et] = emb.weight.detach().float().cpu()
+        cw = torch.zeros(Etp, Etp, 4)
+        cw[:Et, :Et] = ct.weight.detach().float().cpu()
+        cb = torch.zeros(Etp)
+        cb[:Et] = ct.bias.detach().float().cpu()
+        fw = torch.zeros(Etp, Etp)
+        fw[:Et, :Et] = fc.weight.detach().float().cpu()
+        fb = torch.zeros(Etp)
+        fb[:Et] = fc.bias.detach().float().cpu()
+        return table, cw, cb, fw, fb
 
     def pack(self, dev):
         t16 = ops.torch_dtype(self.dtype)
@@ -430,26 +487,43 @@ class MelCodeGenerator(Generator):
         P["up_b"] = ct.bias.detach().float().to(dev).contiguous()
         P["fc_w"], P["fc_b"] = self.fc.weight.detach().to(dev, t16).contiguous(), self.fc.bias.detach().float().to(dev).contiguous()
         P["sp_w"], P["sp_b"] = self.spkr.weight.detach().to(dev, t16).contiguous(), self.spkr.bias.detach().float().to(dev).contiguous()
+        if self.text_supervision:
+            table, cw, cb, fw, fb = self._text_weights()
+            P["t_table"] = table.to(dev, t16).contiguous()
+            P["t_phases"] = [dict(ph, w=ph["w"].to(dev, t16).contiguous()) for ph in convtranspose_phases(cw, 2, 1)]
+            P["t_up_b"], P["t_fc_w"], P["t_fc_b"] = cb.to(dev), fw.to(dev, t16).contiguous(), fb.to(dev)
         self._packed = P
 
-    def forward_rows(self, code, mel, spkr, lens=None):
-        """code int [B,L]; mel fp32 [B,80,2L]; spkr fp32 [B,256]; lens int32 [B] valid code frames (None = all).
-        Returns (wav fp32 [B, 320L], pcm int16 [B, 320L])."""
+    def _check_text(self, t):
+        if self.text_supervision and t is None:
+            raise ValueError("this vocoder is text-supervised (models_multi_input.py:75-77): pass the frame labels (t_label)")
+        if t is not None and not self.text_supervision:
+            raise ValueError("frame labels given to a vocoder without text supervision")
+
+    def forward_rows(self, code, mel, spkr, lens=None, t_label=None):
+        """code int [B,L]; mel fp32 [B,80,2L]; spkr fp32 [B,256]; lens int32 [B] valid code frames (None = all); t_label int
+        [B,L] text frame labels (text-supervised vocoders only).  Returns (wav fp32 [B, 320L], pcm int16 [B, 320L])."""
         dev = code.device
         B, L = code.shape
         nm = self.num_mels
         assert mel.shape == (B, nm, 2 * L), f"mel {tuple(mel.shape)} vs code {tuple(code.shape)}"
+        self._check_text(t_label)
         if lens is None:
             lens = torch.full((B,), L, device=dev, dtype=torch.int32)
+        text = None
+        if t_label is not None:
+            assert t_label.shape == (B, L), f"t_label {tuple(t_label.shape)} vs code {tuple(code.shape)}"
+            tl = t_label.to(torch.int32).contiguous()
+            text = (tl, L, lens, 1)
 
         def fill(P, cat, emb, Cin, dt):
             ops.embedding(code.to(torch.int32).contiguous(), P["table"], emb, B=B, L=L, C=self.h.embedding_dim, lens=lens,
                           dtype=dt)                                                                      # :67
             ops.transpose_ct_to_tc(mel.float().contiguous(), cat, B=B, C=nm, T=2 * L, ldy=Cin, col0=0, lens=lens, len_mul=2,
                                    dtype=dt)                                                             # :65,:73
-        return self._rows(fill, spkr, lens, 1, B, L, dev)
+        return self._rows(fill, spkr, lens, 1, B, L, dev, text)
 
-    def forward_rows_precise(self, code, mel, spkr, lens=None):
+    def forward_rows_precise(self, code, mel, spkr, lens=None, t_label=None):
         """forward_rows at reference precision (parity switch, see _PreciseOps): models_multi_input.py:60-97 with every Linear /
         ConvTranspose as three hi / lo tap-GEMM launches; embedding lookup, concatenation and the layout transposes are torch
         data movement (no arithmetic)."""
@@ -457,6 +531,7 @@ class MelCodeGenerator(Generator):
         B, L = code.shape
         E, nm, t16 = self.h.embedding_dim, self.num_mels, ops.torch_dtype(self.dtype)
         T0 = 2 * L
+        self._check_text(t_label)
         if lens is None:
             lens = torch.full((B,), L, device=dev, dtype=torch.int32)
         po = _PreciseOps(self.dtype, dev)
@@ -467,7 +542,14 @@ class MelCodeGenerator(Generator):
                 "up_b": ct.bias.detach().float().to(dev).contiguous(),
                 "fc": _hi_lo(self.fc.weight, t16, dev), "fc_b": self.fc.bias.detach().float().to(dev).contiguous(),
                 "sp": _hi_lo(self.spkr.weight, t16, dev), "sp_b": self.spkr.bias.detach().float().to(dev).contiguous()}
+            if self.text_supervision:
+                table, cw, cb, fw, fb = self._text_weights()
+                self._front_precise.update(
+                    t_table=table.to(dev), t_up=[dict(ph, w=_hi_lo(ph["w"], t16, dev)) for ph in convtranspose_phases(cw, 2, 1)],
+                    t_up_b=cb.to(dev), t_fc=_hi_lo(fw, t16, dev), t_fc_b=fb.to(dev))
         F = self._front_precise
+        Ct = self._text_dims()[1] if self.text_supervision else 0
+        Cin = nm + 2 * E + Ct
         emb = self.dict.weight.detach().float().to(dev)[code.long()].reshape(B * L, E).contiguous()           # :67
         a = po.split(emb, B, L, E, lens=lens, len_mul=1)
         up = torch.empty(B * T0, E, device=dev, dtype=torch.float32)
@@ -475,37 +557,52 @@ class MelCodeGenerator(Generator):
             po.gemm3(a, ph["w"], up, bias=F["up_b"], M=B * L, N=E, Cin=E, ntaps=ph["ntaps"], mode=MODE_CONV1D, T_out=L, T_in=L,
                      stride=1, dil=-1, off=ph["off"], out_row_mul=2, out_row_add=ph["r"])
         a = po.split(up, B, T0, E, act=2, lens=lens, len_mul=2)                                               # :68 GELU
-        cat = torch.zeros(B * T0, nm + 2 * E, device=dev, dtype=torch.float32)
-        po.gemm3(a, F["fc"], cat[:, nm:], bias=F["fc_b"], M=B * T0, N=E, Cin=E, ldc=nm + 2 * E)               # :70-73
+        cat = torch.zeros(B * T0, Cin, device=dev, dtype=torch.float32)
+        po.gemm3(a, F["fc"], cat[:, nm:], bias=F["fc_b"], M=B * T0, N=E, Cin=E, ldc=Cin)                      # :70-73
         cat[:, :nm] = mel.float().transpose(1, 2).reshape(B * T0, nm)                                         # :65,:73
+        if Ct:                                                                                                # :75-77 layer_text
+            temb = F["t_table"][t_label.long().clamp(0, F["t_table"].shape[0] - 1)].reshape(B * L, Ct).contiguous()
+            a = po.split(temb, B, L, Ct, lens=lens, len_mul=1)
+            up = torch.empty(B * T0, Ct, device=dev, dtype=torch.float32)
+            for ph in F["t_up"]:
+                po.gemm3(a, ph["w"], up, bias=F["t_up_b"], M=B * L, N=Ct, Cin=Ct, ntaps=ph["ntaps"], mode=MODE_CONV1D, T_out=L,
+                         T_in=L, stride=1, dil=-1, off=ph["off"], out_row_mul=2, out_row_add=ph["r"])
+            a = po.split(up, B, T0, Ct, act=2, lens=lens, len_mul=2)
+            po.gemm3(a, F["t_fc"], cat[:, nm + E:], bias=F["t_fc_b"], M=B * T0, N=Ct, Cin=Ct, ldc=Cin)
         sp_in = po.split(spkr.float().contiguous(), B, 1, spkr.shape[1])
         sp = torch.empty(B, E, device=dev, dtype=torch.float32)
         po.gemm3(sp_in, F["sp"], sp, bias=F["sp_b"], M=B, N=E, Cin=spkr.shape[1])                             # :80
-        cat[:, nm + E:] = sp.repeat_interleave(T0, dim=0)                                                     # :81-82
+        cat[:, nm + E + Ct:] = sp.repeat_interleave(T0, dim=0)                                                # :81-82
         return self.generator_rows_precise(cat, lens, B, T0, 2)
 
-    def forward_tokens_rows(self, tokens, mel_rows, spkr, src_lens, token_offset=4):
+    def forward_tokens_rows(self, tokens, mel_rows, spkr, src_lens, token_offset=4, t_rows=None):
         """The in-memory hand-off from stage 1, with no layout or arithmetic left to torch: `tokens` int32
         [B, >= L] are the generator's token rows (unit u = token u + `token_offset`: fairseq's 4 specials come first, and
         dict.unt.txt lists the units in order), `mel_rows` fp32 [B, 2L, 80] the mel head's time-major output
         (model_avhubert.py:276), `src_lens` int32 [B] the clips' VIDEO frame counts (L = 2 x the padded frame count: a unit
         per 20 ms, sequence_generator.py:109).  Equivalent to forward_rows(tokens[:, :L] - 4, mel_rows.transpose(1, 2), spkr,
         2 * src_lens), the file round trip of inference.py:267-274 -> create_dataset.py:366-428 -> dataset_multi_input.py:
-        198-291 whose trimming rule cut = min(mel_len * 160, code_len * 320) is the identity here."""
+        198-291 whose trimming rule cut = min(mel_len * 160, code_len * 320) is the identity here.  `t_rows` int32 [B, >= L]:
+        stage 1's framewise text labels (text-supervised vocoders; create_dataset.py:402-425 hands over pred_text's first line)."""
         dev = tokens.device
         B = tokens.shape[0]
         nm = self.num_mels
         L = mel_rows.shape[1] // 2
         assert mel_rows.shape == (B, 2 * L, nm) and mel_rows.dtype == torch.float32 and mel_rows.is_contiguous()
         assert tokens.dtype == torch.int32 and tokens.shape[1] >= L and tokens.stride(1) == 1
+        self._check_text(t_rows)
+        text = None
+        if t_rows is not None:
+            assert t_rows.dtype == torch.int32 and t_rows.shape[0] == B and t_rows.shape[1] >= L and t_rows.stride(1) == 1
+            text = (t_rows, t_rows.stride(0), src_lens, 2)
 
         def fill(P, cat, emb, Cin, dt):
             ops.embedding_tokens(tokens, P["table"], emb, B=B, L=L, C=self.h.embedding_dim, token_offset=token_offset,
                                  ldt=tokens.stride(0), lens=src_lens, len_mul=2, dtype=dt)
             ops.rows_f32_to_16_masked(mel_rows, cat, B=B, T=2 * L, C=nm, ldy=Cin, col0=0, lens=src_lens, len_mul=4, dtype=dt)
-        return self._rows(fill, spkr, src_lens, 2, B, L, dev)
+        return self._rows(fill, spkr, src_lens, 2, B, L, dev, text)
 
-    def _rows(self, fill, spkr, lens, lm, B, L, dev):
+    def _rows(self, fill, spkr, lens, lm, B, L, dev, text=None):
         """models_multi_input.py:60-97 on channels-last rows.  `fill(P, cat, emb, Cin, dt)` writes the unit embeddings and the
         mel columns of the concat buffer; `lens` counts units of 1 / lm code frames (lm = 1: code frames, 2: video frames)."""
         if self._packed is None or self._packed["table"].device != dev:
@@ -514,7 +611,8 @@ class MelCodeGenerator(Generator):
         t16 = ops.torch_dtype(dt)
         E, nm = h.embedding_dim, self.num_mels
         T0 = 2 * L
-        Cin = nm + 2 * E
+        Ct = P["t_table"].shape[1] if self.text_supervision else 0
+        Cin = nm + 2 * E + Ct
         cat = torch.empty(B * T0, Cin, device=dev, dtype=t16)
         emb = torch.empty(B * L, E, device=dev, dtype=t16)
         fill(P, cat, emb, Cin, dt)
@@ -525,6 +623,19 @@ class MelCodeGenerator(Generator):
                         act=ACT_GELU, lens=lens, mask_T=T0, mask_mul=2 * lm, flags=F_MASK, dtype=dt)
         ops.tapgemm(up, P["fc_w"], cat[:, nm:], M=B * T0, N=E, Cin=E, ldc=Cin, bias=P["fc_b"], lens=lens, mask_T=T0,
                     mask_mul=2 * lm, flags=F_MASK, dtype=dt)                                             # :70-73
+        if Ct:
+            # layer_text (:46-56,75-77): the same three steps as the code branch, into the columns after the code's
+            tok, ldt, tlens, tmul = text
+            temb = torch.empty(B * L, Ct, device=dev, dtype=t16)
+            ops.embedding_tokens(tok, P["t_table"], temb, B=B, L=L, C=Ct, token_offset=0, ldt=ldt, lens=tlens, len_mul=tmul,
+                                 dtype=dt)
+            tup = torch.empty(B * T0, Ct, device=dev, dtype=t16)
+            for ph in P["t_phases"]:
+                ops.tapgemm(temb, ph["w"], tup, M=B * L, N=Ct, Cin=Ct, ntaps=ph["ntaps"], mode=MODE_CONV1D, T_out=L, T_in=L,
+                            stride=1, dil=-1, off=ph["off"], out_row_mul=2, out_row_add=ph["r"], bias=P["t_up_b"],
+                            act=ACT_GELU, lens=lens, mask_T=T0, mask_mul=2 * lm, flags=F_MASK, dtype=dt)
+            ops.tapgemm(tup, P["t_fc_w"], cat[:, nm + E:], M=B * T0, N=Ct, Cin=Ct, ldc=Cin, bias=P["t_fc_b"], lens=lens,
+                        mask_T=T0, mask_mul=2 * lm, flags=F_MASK, dtype=dt)
         spkr = spkr.contiguous()
         if spkr.dtype == torch.float32:
             sp16 = torch.empty(B, spkr.shape[1], device=dev, dtype=t16)
@@ -533,7 +644,7 @@ class MelCodeGenerator(Generator):
             sp16 = spkr.to(t16)
         sp = torch.empty(B, E, device=dev, dtype=t16)
         ops.tapgemm(sp16, P["sp_w"], sp, M=B, N=E, Cin=sp16.shape[1], bias=P["sp_b"], dtype=dt)          # :80
-        ops.broadcast_rows(sp, cat, B=B, T=T0, C=E, ldy=Cin, col0=nm + E, lens=lens, len_mul=2 * lm, dtype=dt)  # :81-82
+        ops.broadcast_rows(sp, cat, B=B, T=T0, C=E, ldy=Cin, col0=nm + E + Ct, lens=lens, len_mul=2 * lm, dtype=dt)  # :81-82
         G = P["gen"]
         c0 = G["pre_b"].shape[0]
         x_l = torch.empty(B * T0, c0, device=dev, dtype=t16)
@@ -545,5 +656,5 @@ class MelCodeGenerator(Generator):
 
     def forward(self, **kwargs):
         """models_multi_input.py:60-97: returns waveform [B,1,320L] in (-1,1)."""
-        wav, _ = self.forward_rows(kwargs["code"], kwargs["mel"], kwargs["spkr"], kwargs.get("lens"))
+        wav, _ = self.forward_rows(kwargs["code"], kwargs["mel"], kwargs["spkr"], kwargs.get("lens"), t_label=kwargs.get("t_label"))
         return wav.unsqueeze(1)

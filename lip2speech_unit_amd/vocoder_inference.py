@@ -58,7 +58,7 @@ def main(argv=None):
         code = {k: torch.from_numpy(v).cuda().unsqueeze(0) for k, v in feats.items()}        # :155
         t0 = time.perf_counter()
         with torch.no_grad():
-            _, pcm = gen.forward_rows(code["code"], code["mel"], code["spkr"])
+            _, pcm = gen.forward_rows(code["code"], code["mel"], code["spkr"], t_label=code.get("t_label"))
         audio = pcm[0].cpu().numpy()                                                          # :79-81
         wall += time.perf_counter() - t0
         audio_s += audio.shape[0] / h.sampling_rate

@@ -53,6 +53,10 @@ def synth_tensor(name: str, shape: Tuple[int, ...], seed: int = 0, dtype=torch.f
             v = uniform(0.7, 1.3)
     elif leaf == "weight" and len(shape) == 2 and ("dict" in name.split(".")[-2:] or name.startswith("dict.")):
         v = normal(1.0)  # nn.Embedding
+    elif name.startswith("layer_text.0."):
+        v = normal(1.0)  # the vocoder's text nn.Embedding (models_multi_input.py:48): unit scale like `dict`
+    elif name.startswith("layer_text.2.") and len(shape) == 3:
+        v = normal(1.0 / np.sqrt(shape[0] * shape[2] / 2.0))  # its ConvTranspose1d [Cin, Cout, k], fan-in as for layer.0
     elif len(shape) >= 2:
         fan_in = n // shape[0]
         if "ups." in name or name.startswith("layer.0"):

@@ -12,6 +12,8 @@ them from parameter names/shapes with lip2speech_unit_amd.weights.synth_state_di
   vocoder.npz    multi_input_vocoder/models_multi_input.py MelCodeGenerator (configs/lrs3/multi_input.json, weight norm removed)
   vocoder_lrs3.npz  the same MelCodeGenerator fed the reference's OWN sample data (datasets/lrs3: units of label/test.unt,
                  mel/*.npy, spk_emb/*.npy of two test clips, trimmed by the rule of dataset_multi_input.py:222-239) - BASELINE configs[0]
+  vocoder_text.npz  the same MelCodeGenerator with text supervision (4000 x 589 text embedding, model_in_dim 925), one code / mel /
+                 speaker input and two t_label rows; also the reference's state-dict names and shapes
   lrs3_sample/   the sample's label files (test.tsv, test.unt, dict.unt.txt): data files, copied verbatim
   hubert_standin.npz  NOT reference code: HuggingFace transformers HubertEncoderStableLayerNorm, an independent port of the
                  fairseq TransformerEncoder that the reference imports but does not vendor.
@@ -148,6 +150,44 @@ def make_vocoder():
     sys.path.pop(0)
 
 
+def make_vocoder_text():
+    """The text-supervised MelCodeGenerator (models_multi_input.py:46-56,75-77; multi_input_vocoder/train.sh:1) with the one
+    text size the reference names, (4000, 589), so model_in_dim = 80 + 128 + 589 + 128 = 925.  Synthetic weights (seed 17), the
+    same code / mel / speaker run with two different t_label rows so a test sees the branch matter."""
+    sys.path.insert(0, f"{REF}/speech-resynthesis")
+    sys.path.insert(0, f"{REF}/multi_input_vocoder")
+    from models_multi_input import MelCodeGenerator
+    from utils import AttrDict
+    h = AttrDict(json.load(open(f"{REF}/multi_input_vocoder/configs/lrs3/multi_input.json")))
+    h.text_supervision = True
+    h.num_embeddings_text, h.embedding_dim_text, h.model_in_dim = 4000, 589, 925
+    g = MelCodeGenerator(h).eval()
+    names = spec(g)
+    sd = weights.synth_state_dict(names, seed=17)
+    g.load_state_dict(sd, strict=True)
+    g.remove_weight_norm()
+    gen = torch.Generator().manual_seed(404)
+    L = 20
+    code = torch.randint(0, 200, (1, L), generator=gen)
+    mel = -11.5 + 11.6 * torch.rand(1, 80, 2 * L, generator=gen)
+    spk = torch.rand(1, 256, generator=gen).relu()
+    spk = spk / spk.norm()
+    t_label = torch.randint(1, 4000, (2, L), generator=gen)
+    t_label[:, ::3] = 0                                   # CTC blanks among the frame labels
+    wavs = []
+    with torch.no_grad():
+        for r in range(2):
+            wavs.append(g(code=code, mel=mel, spkr=spk, t_label=t_label[r:r + 1]).numpy())
+    wav = np.concatenate(wavs, 0)
+    pcm = (wav[:, 0] * 32768.0).astype("int16")
+    np.savez_compressed(os.path.join(OUT, "vocoder_text.npz"), seed=17, code=code.numpy(), mel=mel.numpy(), spkr=spk.numpy(),
+                        t_label=t_label.numpy(), wav=wav, pcm=pcm, names=np.array([n for n, _ in names]),
+                        shapes=np.array([",".join(str(d) for d in sh) for _, sh in names]),
+                        config=json.dumps({"num_embeddings_text": 4000, "embedding_dim_text": 589, "model_in_dim": 925}))
+    sys.path.pop(0)
+    sys.path.pop(0)
+
+
 LRS3_CLIPS = ["test/UmvOgW6iV2s/00007", "test/62cNtvx6P8E/00001"]   # line 1 of test.tsv/.unt; the shortest clip (SURVEY App. A)
 
 
@@ -249,7 +289,8 @@ def make_hubert_standin():
 if __name__ == "__main__":
     os.makedirs(OUT, exist_ok=True)
     torch.set_num_threads(8)
-    which = sys.argv[1:] or ["frontend", "frontend_swish", "raven", "conformer", "vocoder", "vocoder_lrs3", "hubert_standin"]
+    which = sys.argv[1:] or ["frontend", "frontend_swish", "raven", "conformer", "vocoder", "vocoder_lrs3", "hubert_standin",
+                                 "vocoder_text"]
     for w in which:
         print("making", w, flush=True)
         globals()["make_" + w]()
