@@ -43,7 +43,7 @@ def mha(sd, p, x, key_padding_mask, heads):
     s = q @ k.transpose(-1, -2)
     if key_padding_mask is not None:
         s = s.masked_fill(key_padding_mask[:, None, None, :], float("-inf"))
-    a = torch.softmax(s.float(), dim=-1)
+    a = torch.softmax(s.to(torch.promote_types(s.dtype, torch.float32)), dim=-1)  # fp32 (fp64 stays fp64)
     o = (a @ v).transpose(1, 2).reshape(B, T, C)
     return _lin(sd, p + ".out_proj", o)
 

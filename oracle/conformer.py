@@ -15,12 +15,12 @@ def _ln(sd, p, x):
     return F.layer_norm(x, (x.shape[-1],), sd[p + ".weight"], sd[p + ".bias"], 1e-12)  # layer_norm.py:21
 
 
-def rel_pos_table(T, d_model):
+def rel_pos_table(T, d_model, dtype=torch.float32):
     """RelPositionalEncoding.extend_pe + forward slice (embedding.py:172-217): returns pos_emb [1, 2T-1, d];
-    row k encodes relative position (T-1-k)."""
-    rel = torch.arange(T - 1, -T, -1, dtype=torch.float32).unsqueeze(1)  # T-1 ... -(T-1)
-    div = torch.exp(torch.arange(0, d_model, 2, dtype=torch.float32) * -(math.log(10000.0) / d_model))
-    pe = torch.zeros(2 * T - 1, d_model)
+    row k encodes relative position (T-1-k).  `dtype`: the table is built in it (fp64 for the tests' fp64 reference)."""
+    rel = torch.arange(T - 1, -T, -1, dtype=dtype).unsqueeze(1)  # T-1 ... -(T-1)
+    div = torch.exp(torch.arange(0, d_model, 2, dtype=dtype) * -(math.log(10000.0) / d_model))
+    pe = torch.zeros(2 * T - 1, d_model, dtype=dtype)
     pe[:, 0::2] = torch.sin(rel * div)
     pe[:, 1::2] = torch.cos(rel * div)
     return pe.unsqueeze(0)
@@ -87,7 +87,7 @@ def espnet_encoder_after_frontend(sd, p, x, masks, layers=12, heads=8, taps=None
     x = _lin(sd, p + ".embed.0", x)
     d = x.shape[-1]
     x = x * math.sqrt(d)                       # embedding.py:211
-    pos_emb = rel_pos_table(x.shape[1], d)
+    pos_emb = rel_pos_table(x.shape[1], d, x.dtype if x.dtype == torch.float64 else torch.float32)
     for i in range(layers):
         x = encoder_layer(sd, f"{p}.encoders.{i}", x, pos_emb, masks, heads)
         if taps is not None:

@@ -67,7 +67,10 @@ def _attn_ref(q, k, v, lens, pos=None, u=None, vb=None):
                                           # sequence-resident rel-pos kernel (T <= 224): more clips than block slots, ragged
                                           # lengths, the largest T it takes, tiny T
                                           (70, 200, 8, True), (3, 224, 8, True), (2, 17, 8, True), (5, 1, 2, True),
-                                          (40, 33, 8, True), (2, 225, 8, True)])
+                                          (40, 33, 8, True), (2, 225, 8, True),
+                                          # the 24-s clips: conformer rel-pos at T = 1200 (2 399 positions) on the tiled
+                                          # kernel's 128-row query blocks, alone and ragged; encoder attention at T = 600, H = 16
+                                          (1, 1200, 8, True), (2, 1200, 8, True), (2, 600, 16, False)])
 def test_attention(dt, B, T, H, relpos):
     g = torch.Generator().manual_seed(B * 1000 + T)
     d = 64
@@ -116,7 +119,8 @@ def _attn_ref_rounded(q, k, v, lens, pos, u, vb, dt):
 
 
 @pytest.mark.parametrize("dt", [ops.F16, ops.BF16])
-@pytest.mark.parametrize("T,lens", [(150, [150, 97]), (200, [200, 101]), (100, [99, 100]), (257, [257, 3]), (31, [31, 1])])
+@pytest.mark.parametrize("T,lens", [(150, [150, 97]), (200, [200, 101]), (100, [99, 100]), (257, [257, 3]), (31, [31, 1]),
+                                    (1200, [1200, 50])])
 def test_glu_dwconv_swish(dt, T, lens):
     """T = 150, 257, 31 run on the 128-step tile, T = 200 / 100 on the 100-step tile (the launcher takes whichever wastes
     fewer rows); ragged lengths, a clip shorter than the conv's half-width."""
