@@ -27,10 +27,18 @@
 extern "C" {
 #endif
 
-#define L2S_ABI_VERSION 15
+#define L2S_ABI_VERSION 16
 
-/* element type of 16-bit operands */
-enum { L2S_F16 = 0, L2S_BF16 = 1 };
+/* element type of the operands: fp16 / bf16 storage with fp32 accumulation, or L2S_F32 (ABI 16) = the reference's default
+ * precision: operands, activations and accumulation all fp32.  With L2S_F32 every pointer documented as "16-bit" below is an
+ * fp32 pointer (leading dimensions stay in elements) and L2S_F_OUT_F32 / L2S_F_RES_F32 / x_is_f32 / y_is_f32 / v_is_f32 are
+ * implied.  Served in fp32: l2s_tapgemm (all modes, activations and flags; no ktab), l2s_attention, l2s_layernorm,
+ * l2s_glu_dwconv_swish, l2s_stem_conv3d, l2s_maxpool2d_3x3s2, l2s_avgpool_hw, l2s_preprocess_frames, l2s_repeat2_cast,
+ * l2s_broadcast_rows, l2s_rows_f32_to_16_masked and the two casts (plain copies).  The fused / resident forms
+ * (l2s_stem_pool_fused*, l2s_basicblock_fused, l2s_basiclayer_fused, l2s_basicstage128_tail_fused,
+ * l2s_splitk_reduce_layernorm, a ktab descriptor) and the vocoder kernels answer L2S_EUNSUPPORTED or L2S_EINVAL.
+ * fp32 epilogues use erff / expf / tanhf and IEEE division: only the summation order separates them from an fp32 reference. */
+enum { L2S_F16 = 0, L2S_BF16 = 1, L2S_F32 = 2 };
 
 /* error codes */
 enum { L2S_OK = 0, L2S_EINVAL = -1, L2S_ESHAPE = -2, L2S_EALIGN = -3, L2S_EUNSUPPORTED = -4 };
@@ -120,10 +128,14 @@ const char* l2s_build_info(void);
 
 int l2s_tapgemm(const l2s_gemm_desc* host_desc, void* stream);
 /* block tile the launcher picks for this descriptor, as BM*1000+BN (profiling aid: names the kernel instantiation);
- * 256256 = the phase-staggered kernel, 999064 / 999128 = the patch conv kernel at 64 / 128 channels */
+ * 256256 = the phase-staggered kernel, 999064 / 999128 = the patch conv kernel at 64 / 128 channels,
+ * L2S_VARIANT_F32 = the fp32 kernel (128 x 128 tile on v_mfma_f32_32x32x2_f32, csrc/tapgemm_f32.hip) */
+#define L2S_VARIANT_F32 2128128
 int l2s_tapgemm_variant(const l2s_gemm_desc* host_desc);
 /* epilogue family (0..9) of the kernel instantiation the launcher picks: every kernel is built once per family of
- * (flags, activation) so that a launch carries one epilogue's code only (profiling aid, names the instantiation) */
+ * (flags, activation) so that a launch carries one epilogue's code only (profiling aid, names the instantiation);
+ * L2S_EPI_FAMILY_F32 for an fp32 descriptor (one run-time epilogue) */
+#define L2S_EPI_FAMILY_F32 32
 int l2s_tapgemm_epilogue_family(const l2s_gemm_desc* host_desc);
 
 /*

@@ -9,11 +9,11 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("L2S_LIB_PATH") or os.path.join(_HERE, "liblip2speech_hip.so")  # env override: A/B builds
 
 # mirrors of the header's enums
-F16, BF16 = 0, 1
+F16, BF16, F32 = 0, 1, 2   # F32: operands, activations and accumulation all fp32 (the reference's default precision)
 ACT_NONE, ACT_RELU, ACT_GELU, ACT_SWISH, ACT_PRELU, ACT_LRELU, ACT_TANH = range(7)
 F_RES_PRE, F_RES_POST, F_ACCUM, F_DUAL, F_MASK, F_OUT_F32, F_RES_F32 = (1 << i for i in range(7))
 MODE_LINEAR, MODE_CONV1D, MODE_CONV2D = 0, 1, 2
-ABI_VERSION = 15
+ABI_VERSION = 16
 
 _ERR = {-1: "L2S_EINVAL", -2: "L2S_ESHAPE", -3: "L2S_EALIGN", -4: "L2S_EUNSUPPORTED"}
 

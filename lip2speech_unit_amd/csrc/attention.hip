@@ -524,6 +524,10 @@ __global__ __launch_bounds__(1024) void attention_resident_kernel(const uint16_t
 
 }  // namespace
 
+// f32_kernels.hip
+int l2s_f32_attention(const void* qkv, int ldq, void* out, int ldo, const void* pos, int ldp, const float* bias_u, const float* bias_v,
+                      const int32_t* lens, int len_mul, int B, int T, int H, hipStream_t st);
+
 extern "C" int l2s_attention(const void* qkv, int ldq, void* out, int ldo, const void* pos, int ldp,
                              const float* bias_u, const float* bias_v, const int32_t* lens, int len_mul, int B, int T,
                              int H, int dtype, void* stream) {
@@ -534,6 +538,10 @@ extern "C" int l2s_attention(const void* qkv, int ldq, void* out, int ldo, const
   if (pos && (!bias_u || !bias_v || (ldp & 7) || ldp < H * D || ((uintptr_t)pos & 15))) return L2S_EINVAL;
   if (lens && len_mul <= 0) return L2S_EINVAL;
   hipStream_t st = (hipStream_t)stream;
+  if (dtype == L2S_F32) {   // qkv, pos and out are fp32; any T (no resident form)
+    if ((uintptr_t)out & 15) return L2S_EALIGN;
+    return l2s_f32_attention(qkv, ldq, out, ldo, pos, ldp, bias_u, bias_v, lens, len_mul, B, T, H, st);
+  }
   const uint16_t* q = (const uint16_t*)qkv;
   uint16_t* o = (uint16_t*)out;
   const uint16_t* pp = (const uint16_t*)pos;

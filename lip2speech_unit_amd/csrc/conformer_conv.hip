@@ -60,12 +60,17 @@ __global__ __launch_bounds__(256) void glu_dwconv_kernel(const uint16_t* __restr
 
 }  // namespace
 
+// f32_kernels.hip
+int l2s_f32_glu_dwconv_swish(const void* x, const float* w, const float* bias, void* y, const int32_t* lens, int len_mul, int B, int T,
+                             int C, int k, hipStream_t st);
+
 extern "C" int l2s_glu_dwconv_swish(const void* x, const float* w, const float* bias, void* y, const int32_t* lens,
                                     int len_mul, int B, int T, int C, int k, int dtype, void* stream) {
   if (!x || !w || !bias || !y) return L2S_EINVAL;
   if (B <= 0 || T <= 0 || C <= 0) return L2S_ESHAPE;
   if (k <= 0 || k > KMAX || !(k & 1)) return L2S_EUNSUPPORTED;
   if (C % CT) return L2S_EALIGN;
+  if (dtype == L2S_F32) return l2s_f32_glu_dwconv_swish(x, w, bias, y, lens, len_mul, B, T, C, k, (hipStream_t)stream);
   // rows computed = tiles * TT: take the tile length that wastes fewer of them (ties: the longer tile, less halo)
   const int r128 = ((T + 127) / 128) * 128, r100 = ((T + 99) / 100) * 100;
   const bool use100 = r100 + ((T + 99) / 100) * 10 < r128 + ((T + 127) / 128) * 10;

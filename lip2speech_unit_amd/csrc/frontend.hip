@@ -555,6 +555,13 @@ inline int grid_for(int64_t total, int block) {
 
 }  // namespace
 
+// f32_kernels.hip
+int l2s_f32_stem_conv3d(const void* x, const void* w, const float* bias, const float* slope, void* y, int B, int T, hipStream_t st);
+int l2s_f32_maxpool2d_3x3s2(const void* x, void* y, int N, int H, int W, int C, hipStream_t st);
+int l2s_f32_avgpool_hw(const void* x, void* y, int N, int HW, int C, hipStream_t st);
+int l2s_f32_preprocess_frames(const uint8_t* frames, void* y, int64_t nframes, int Hin, int Win, int crop, float mean, float std,
+                              hipStream_t st);
+
 extern "C" int l2s_stem_conv3d(const void* x, int x_is_f32, const void* w, const float* bias, const float* slope,
                                void* y, int B, int T, int H, int W, int dtype, void* stream) {
   if (!x || !w || !bias || !y) return L2S_EINVAL;   // slope == NULL selects Swish (ESPnet Conv3dResNet) instead of PReLU
@@ -563,6 +570,7 @@ extern "C" int l2s_stem_conv3d(const void* x, int x_is_f32, const void* w, const
   if (((uintptr_t)w & 15) || ((uintptr_t)y & 15)) return L2S_EALIGN;
   dim3 grid(2, B * T);
   hipStream_t st = (hipStream_t)stream;
+  if (dtype == L2S_F32) return x_is_f32 ? l2s_f32_stem_conv3d(x, w, bias, slope, y, B, T, st) : L2S_EINVAL;   // fp32 frames only
   const uint16_t* wp = (const uint16_t*)w;
   uint16_t* yp = (uint16_t*)y;
   if (dtype == L2S_F16) {
@@ -589,6 +597,7 @@ static int stem_pool_dispatch(const void* x, int xk, const void* w, const float*
                               int T, int dtype, StemU8 u8, void* stream) {
   if (!x || !w || !bias || !y) return L2S_EINVAL;   // slope == NULL selects Swish (ESPnet Conv3dResNet) instead of PReLU
   if (B <= 0 || T <= 0) return L2S_ESHAPE;
+  if (dtype == L2S_F32) return L2S_EUNSUPPORTED;    // fp32 runs l2s_stem_conv3d + l2s_maxpool2d_3x3s2
   if (((uintptr_t)w & 15) || ((uintptr_t)y & 15)) return L2S_EALIGN;
   if (xk != 2 && ((uintptr_t)x & 15)) return L2S_EALIGN;   // 16-bit / fp32 frames are fetched as 8- / 16-byte quads (uint8: any address)
   // frames per block: every block pays the weight fetch, the LDS initialisation and a five-slab window once; longer chunks
@@ -637,6 +646,7 @@ extern "C" int l2s_maxpool2d_3x3s2(const void* x, void* y, int N, int H, int W, 
   const int Ho = (H + 2 - 3) / 2 + 1, Wo = (W + 2 - 3) / 2 + 1;
   const int64_t total = (int64_t)N * Ho * Wo * (C / 8);
   hipStream_t st = (hipStream_t)stream;
+  if (dtype == L2S_F32) return l2s_f32_maxpool2d_3x3s2(x, y, N, H, W, C, st);
   if (dtype == L2S_F16)
     hipLaunchKernelGGL((maxpool_kernel<ElemF16>), dim3(grid_for(total, 256)), dim3(256), 0, st, (const uint16_t*)x,
                        (uint16_t*)y, N, H, W, C, Ho, Wo);
@@ -654,6 +664,7 @@ extern "C" int l2s_avgpool_hw(const void* x, void* y, int N, int HW, int C, int 
   if (C & 7) return L2S_EALIGN;
   const int64_t total = (int64_t)N * (C / 8);
   hipStream_t st = (hipStream_t)stream;
+  if (dtype == L2S_F32) return l2s_f32_avgpool_hw(x, y, N, HW, C, st);
   if (dtype == L2S_F16)
     hipLaunchKernelGGL((avgpool_kernel<ElemF16>), dim3(grid_for(total, 256)), dim3(256), 0, st, (const uint16_t*)x,
                        (uint16_t*)y, N, HW, C);
@@ -672,6 +683,7 @@ extern "C" int l2s_preprocess_frames(const uint8_t* frames, void* y, int B, int 
   const int64_t nf = (int64_t)B * T;
   const int64_t total = nf * crop * crop;
   hipStream_t st = (hipStream_t)stream;
+  if (dtype == L2S_F32) return l2s_f32_preprocess_frames(frames, y, nf, Hin, Win, crop, mean, std, st);
   if (dtype == L2S_F16)
     hipLaunchKernelGGL((preprocess_kernel<ElemF16>), dim3(grid_for(total, 256)), dim3(256), 0, st, frames,
                        (uint16_t*)y, nf, Hin, Win, crop, mean, 1.0f / std);

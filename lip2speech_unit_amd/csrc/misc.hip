@@ -267,6 +267,10 @@ __global__ __launch_bounds__(256) void conv_post16_kernel(const float* __restric
 
 }  // namespace
 
+// f32_kernels.hip: fp32 row copy (rep = 2: the x2 time repeat) / per-clip broadcast, rows past lens[b]*len_mul zeroed
+int l2s_f32_rows(const float* x, int ldx, void* y, int ldy, int col0, const int32_t* lens, int len_mul, int64_t rows, int T, int C, int rep,
+                 int bcast, hipStream_t st);
+
 #define DISPATCH_ET(dtype, CALL_F16, CALL_BF16) \
   if ((dtype) == L2S_F16) { CALL_F16; } else if ((dtype) == L2S_BF16) { CALL_BF16; } else return L2S_EINVAL;
 
@@ -276,6 +280,7 @@ extern "C" int l2s_repeat2_cast(const float* x, void* y, int B, int T, int C, in
   if (C & 3) return L2S_EALIGN;
   const int64_t rows = (int64_t)B * T;
   hipStream_t st = (hipStream_t)stream;
+  if (dtype == L2S_F32) return l2s_f32_rows(x, C, y, C, 0, nullptr, 1, rows, T, C, 2, 0, st);
   dim3 g(grid_for(rows * (C >> 2), 256)), blk(256);
   DISPATCH_ET(dtype,
               hipLaunchKernelGGL((repeat2_cast_kernel<ElemF16>), g, blk, 0, st, x, (uint16_t*)y, rows, C),
@@ -316,6 +321,7 @@ extern "C" int l2s_cast_f32_to_16(const float* x, int ldx, void* y, int ldy, int
   if (!x || !y) return L2S_EINVAL;
   if (M <= 0 || C <= 0) return L2S_ESHAPE;
   hipStream_t st = (hipStream_t)stream;
+  if (dtype == L2S_F32) return l2s_f32_rows(x, ldx, y, ldy, 0, nullptr, 1, M, M, C, 1, 0, st);   // a plain copy
   dim3 g(grid_for((int64_t)M * C, 256)), blk(256);
   DISPATCH_ET(dtype,
               hipLaunchKernelGGL((cast_to16_kernel<ElemF16>), g, blk, 0, st, x, ldx, (uint16_t*)y, ldy, (int64_t)M, C),
@@ -328,6 +334,7 @@ extern "C" int l2s_cast_16_to_f32(const void* x, int ldx, float* y, int ldy, int
   if (!x || !y) return L2S_EINVAL;
   if (M <= 0 || C <= 0) return L2S_ESHAPE;
   hipStream_t st = (hipStream_t)stream;
+  if (dtype == L2S_F32) return l2s_f32_rows((const float*)x, ldx, y, ldy, 0, nullptr, 1, M, M, C, 1, 0, st);   // a plain copy
   dim3 g(grid_for((int64_t)M * C, 256)), blk(256);
   DISPATCH_ET(dtype,
               hipLaunchKernelGGL((cast_to32_kernel<ElemF16>), g, blk, 0, st, (const uint16_t*)x, ldx, y, ldy, (int64_t)M, C),
@@ -341,6 +348,8 @@ extern "C" int l2s_broadcast_rows(const void* v, int ldv, void* y, int ldy, int 
   if (!v || !y) return L2S_EINVAL;
   if (B <= 0 || T <= 0 || C <= 0 || col0 < 0) return L2S_ESHAPE;
   hipStream_t st = (hipStream_t)stream;
+  if (dtype == L2S_F32)   // v and y are fp32
+    return v_is_f32 ? l2s_f32_rows((const float*)v, ldv, y, ldy, col0, lens, len_mul, (int64_t)B * T, T, C, 1, 1, st) : L2S_EINVAL;
   dim3 g(grid_for((int64_t)B * T * C, 256)), blk(256);
   uint16_t* yp = (uint16_t*)y;
   if (v_is_f32) {
@@ -404,6 +413,7 @@ extern "C" int l2s_rows_f32_to_16_masked(const float* x, int ldx, void* y, int l
   if (B <= 0 || T <= 0 || C <= 0 || col0 < 0 || len_mul <= 0) return L2S_ESHAPE;
   if ((C & 3) || (ldx & 3) || (ldy & 3) || (col0 & 3)) return L2S_EALIGN;
   hipStream_t st = (hipStream_t)stream;
+  if (dtype == L2S_F32) return l2s_f32_rows(x, ldx, y, ldy, col0, lens, len_mul, (int64_t)B * T, T, C, 1, 0, st);
   dim3 g(grid_for((int64_t)B * T * (C >> 2), 256)), blk(256);
   DISPATCH_ET(dtype,
               hipLaunchKernelGGL((rows_to16_masked_kernel<ElemF16>), g, blk, 0, st, x, ldx, (uint16_t*)y, ldy, col0, lens, len_mul, B, T, C),

@@ -283,6 +283,10 @@ int launch_ln(const void* x, int xf, int ldx, const float* g, const float* b, fl
 
 }  // namespace
 
+// f32_kernels.hip
+int l2s_f32_layernorm(const void* x, int ldx, const float* gamma, const float* beta, float eps, void* y, int ldy, void* y2, int ldy2,
+                      int M, int C, int zp, const int32_t* lens, int len_mul, int mask_T, hipStream_t st);
+
 extern "C" int l2s_layernorm(const void* x, int x_is_f32, int ldx, const float* gamma, const float* beta, float eps,
                              void* y, int y_is_f32, int ldy, void* y2, int ldy2, int M, int C, int zero_prefix,
                              const int32_t* lens, int len_mul, int mask_T, int dtype, void* stream) {
@@ -292,6 +296,8 @@ extern "C" int l2s_layernorm(const void* x, int x_is_f32, int ldx, const float* 
   if (lens && (len_mul <= 0 || mask_T <= 0)) return L2S_EINVAL;
   if ((C & 3) || (zero_prefix & 3) || (ldx & 3) || (ldy & 3) || (y2 && (ldy2 & 3))) return L2S_EALIGN;
   hipStream_t st = (hipStream_t)stream;
+  if (dtype == L2S_F32)   // x, y and y2 are all fp32
+    return l2s_f32_layernorm(x, ldx, gamma, beta, eps, y, ldy, y2, ldy2, M, C, zero_prefix, lens, len_mul, mask_T, st);
   if (dtype == L2S_F16)
     return launch_ln<ElemF16>(x, x_is_f32, ldx, gamma, beta, eps, y, y_is_f32, ldy, (uint16_t*)y2, ldy2, M, C, zero_prefix, lens, len_mul, mask_T, st);
   if (dtype == L2S_BF16)
@@ -312,5 +318,6 @@ extern "C" int l2s_splitk_reduce_layernorm(const float* P, int ldp, int S, float
   hipStream_t st = (hipStream_t)stream;
   if (dtype == L2S_F16) return launch_splitk_ln<ElemF16>(P, ldp, S, x, ldx, gamma, beta, eps, y, y_is_f32, ldy, M, C, lens, len_mul, mask_T, st);
   if (dtype == L2S_BF16) return launch_splitk_ln<ElemBF16>(P, ldp, S, x, ldx, gamma, beta, eps, y, y_is_f32, ldy, M, C, lens, len_mul, mask_T, st);
+  if (dtype == L2S_F32) return L2S_EUNSUPPORTED;   // fp32 runs the one-launch Linear and l2s_layernorm
   return L2S_EINVAL;
 }

@@ -49,6 +49,8 @@ int l2s_phasegemm_ktab_launch(const l2s_gemm_desc& d, hipStream_t st);
 // patchconv.hip: LDS-resident-patch kernel for the Cin = N = 64 stride-1 convolutions
 bool l2s_patchconv_eligible(const l2s_gemm_desc& d);
 int l2s_patchconv_launch(const l2s_gemm_desc& d, hipStream_t st);
+// tapgemm_f32.hip: the fp32 reference-precision kernel (desc.dtype = L2S_F32)
+int l2s_tapgemm_f32_launch(const l2s_gemm_desc& d, hipStream_t st);
 static bool patch_enabled() {
   static const bool on = [] { const char* e = getenv("L2S_NO_PATCHCONV"); return !(e && atoi(e)); }();  // tuning aid
   return on;
@@ -61,6 +63,17 @@ extern "C" int l2s_tapgemm(const l2s_gemm_desc* hd, void* stream) {
   if (d.M <= 0 || d.N <= 0 || d.Cin <= 0 || d.ntaps <= 0) return L2S_ESHAPE;
   if (d.groups <= 0) d.groups = 1;
   if (d.out_row_mul <= 0) d.out_row_mul = 1;
+  if (d.dtype == L2S_F32) {   // fp32 operands: own alignment rules (16-byte chunks of four floats, scalar epilogue)
+    if (((uintptr_t)d.A & 15) || ((uintptr_t)d.W & 15) || ((uintptr_t)d.C & 3)) return L2S_EALIGN;
+    if ((d.flags & (L2S_F_RES_PRE | L2S_F_RES_POST)) && !d.R) return L2S_EINVAL;
+    if ((d.flags & L2S_F_DUAL) && !d.C2) return L2S_EINVAL;
+    if ((d.flags & L2S_F_MASK) && (!d.lens || d.mask_T <= 0 || d.mask_mul <= 0)) return L2S_EINVAL;
+    if (d.act == L2S_ACT_PRELU && !d.slope) return L2S_EINVAL;
+    if (d.mode == L2S_MODE_CONV1D && (d.T_out <= 0 || d.T_in <= 0)) return L2S_ESHAPE;
+    if (d.mode == L2S_MODE_CONV2D && (d.Ho <= 0 || d.Wo <= 0 || d.Hi <= 0 || d.Wi <= 0 || d.KW <= 0)) return L2S_ESHAPE;
+    if ((int64_t)d.M * d.out_row_mul + d.out_row_add >= ((int64_t)1 << 31)) return L2S_EUNSUPPORTED;
+    return l2s_tapgemm_f32_launch(d, (hipStream_t)stream);
+  }
   // 16-byte vector loads of A/W chunks, 8/16-byte vector epilogue
   if ((d.Cin & 7) || (d.lda & 7) || (d.N & 3) || (d.ldc & 3) || (d.a_gstride & 7) || (d.c_gstride & 3) ||
       (d.w_gstride & 7))
@@ -84,6 +97,7 @@ extern "C" int l2s_tapgemm(const l2s_gemm_desc* hd, void* stream) {
 
 extern "C" int l2s_tapgemm_variant(const l2s_gemm_desc* hd) {
   if (!hd || hd->M <= 0 || hd->N <= 0) return L2S_EINVAL;
+  if (hd->dtype == L2S_F32) return hd->ktab ? L2S_EUNSUPPORTED : L2S_VARIANT_F32;   // tapgemm_f32.hip: one 128 x 128 tile
   if (hd->ktab || l2s_phasegemm_eligible(*hd)) return 256256;           // phasegemm.hip
   if (patch_enabled() && l2s_patchconv_eligible(*hd)) return 999000 + hd->N;  // patchconv.hip: 999064 / 999128
   return pick_tile(hd->M, hd->N, hd->groups > 0 ? hd->groups : 1);
@@ -91,5 +105,6 @@ extern "C" int l2s_tapgemm_variant(const l2s_gemm_desc* hd) {
 
 extern "C" int l2s_tapgemm_epilogue_family(const l2s_gemm_desc* hd) {
   if (!hd) return L2S_EINVAL;
+  if (hd->dtype == L2S_F32) return L2S_EPI_FAMILY_F32;   // one instantiation per mode, the epilogue selects at run time
   return l2s::pick_epilogue(hd->flags, hd->act);
 }

@@ -152,7 +152,8 @@ def build_model(cfg, task, logger=None, checkpoint_path=None):
     (default common_eval.path; "synthetic[:seed]" = the build-owned seeded generator), on the GPU in eval mode."""
     from .conformer import ConformerConfig
     from .hubert import AVHubertConfig
-    dtype = ops.BF16 if cfg["dtype"] == "bf16" else ops.F16
+    from .model import parse_dtype
+    dtype = parse_dtype(cfg["dtype"])[0]      # dtype=f32: stage 1 in fp32, the reference's default precision (its fp16=false)
     model = MultiTargetAVHubertEncoderModel.build_model(
         task=task, dtype=dtype, w2v_cfg=AVHubertConfig(encoder_layers=int(cfg["model.encoder_layers"])),
         conformer_cfg=ConformerConfig(conformer_layers=int(cfg["model.conformer_layers"])))
@@ -175,7 +176,8 @@ def build_vocoder(cfg):
     from .vocoder import AttrDict, MelCodeGenerator
     h = AttrDict(json.load(open(cfg["vocoder.config"])))
     h.text_supervision = bool(int(os.environ.get("TEXT_SUPERVISION", 0)))   # multi_input_vocoder/inference.py:112
-    voc = MelCodeGenerator(h, dtype=ops.BF16 if cfg["dtype"] == "bf16" else ops.F16)
+    from .model import parse_dtype
+    voc = MelCodeGenerator(h, dtype=parse_dtype(cfg["dtype"])[1])   # dtype=f32 is a stage-1 switch: fp16 operands here
     path = cfg["vocoder.checkpoint"]
     if path is None or str(path).startswith("synthetic"):
         seed = int(str(path).split(":", 1)[1]) if path and ":" in str(path) else 1

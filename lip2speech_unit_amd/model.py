@@ -102,8 +102,31 @@ class MultiTargetRAVENEncoderModelConfig(MultiTargetEncoderModelConfig):
 
 
 def env_dtype():
-    """fairseq's `build_model(cfg, task)` has no precision argument: L2S_DTYPE=bf16 selects bf16 operands (default fp16)."""
-    return ops.BF16 if os.environ.get("L2S_DTYPE", "f16").lower() in ("bf16", "bfloat16") else ops.F16
+    """fairseq's `build_model(cfg, task)` has no precision argument: L2S_DTYPE=bf16 selects bf16 operands, L2S_DTYPE=f32 the
+    fp32 reference-precision mode of stage 1 (default fp16)."""
+    v = os.environ.get("L2S_DTYPE", "f16").lower()
+    if v in ("f32", "fp32", "float32"):
+        return ops.F32
+    return ops.BF16 if v in ("bf16", "bfloat16") else ops.F16
+
+
+def parse_dtype(name):
+    """The `dtype=` switch of the CLIs and servers -> (stage-1 operand type, vocoder operand type).  f32 selects fp32 for stage 1
+    only (the reference's default precision, `fp16=false` there); the vocoder keeps fp16 operands - its `precise` switch is
+    its own matter."""
+    n = str(name).lower()
+    if n in ("f32", "fp32", "float32"):
+        return ops.F32, ops.F16
+    if n in ("bf16", "bfloat16"):
+        return ops.BF16, ops.BF16
+    if n in ("f16", "fp16", "float16", "half"):
+        return ops.F16, ops.F16
+    raise ValueError(f"dtype={name!r}: expected f16, bf16 or f32")
+
+
+def refuse_f32(dtype, what):
+    if dtype == ops.F32:
+        raise NotImplementedError(f"{what}: the fp32 (dtype=f32) mode is built for the multi_target_avhubert stage-1 path only")
 
 AVSR_FRONTEND_WEIGHT_SUM = -27874.6481   # model.py:137-144: known-answer check of the pretrained Auto-AVSR frontend
 
@@ -168,6 +191,7 @@ class MultiTargetEncoderModel(ModelBase):
     @classmethod
     def build_model(cls, cfg=None, task=None, dtype=None, conformer_cfg: ConformerConfig = None):
         dtype = env_dtype() if dtype is None else dtype
+        refuse_f32(dtype, "multi_target (Conv3dResNet frontend)")
         conformer_cfg = conformer_cfg or ConformerConfig.from_model_cfg(cfg)
         tgt_dict = getattr(task, "target_dictionary", None) if task is not None else None
         if tgt_dict is not None:

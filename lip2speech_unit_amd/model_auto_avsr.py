@@ -15,7 +15,7 @@ import torch.nn as nn
 from . import ops
 from .conformer import Conformer, ConformerConfig, Encoder
 from .conv3d_extractor import Conv3dResNet
-from .model import MultiTargetAutoAVSREncoderModelConfig, env_dtype
+from .model import MultiTargetAutoAVSREncoderModelConfig, env_dtype, refuse_f32
 from .plugin import ModelBase, cfg_get, register_model
 
 
@@ -86,6 +86,7 @@ class MultiTargetAutoAVSREncoderModel(ModelBase):
     def build_model(cls, cfg=None, task=None, dtype=None, encoder_cfg: AutoAVSRConfig = None,
                     conformer_cfg: ConformerConfig = None):
         dtype = env_dtype() if dtype is None else dtype
+        refuse_f32(dtype, "multi_target_auto_avsr")
         encoder_cfg = encoder_cfg or AutoAVSRConfig.from_model_cfg(cfg)
         conformer_cfg = conformer_cfg or ConformerConfig.from_model_cfg(cfg)
         tgt_dict = getattr(task, "target_dictionary", None) if task is not None else None

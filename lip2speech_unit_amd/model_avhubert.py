@@ -127,7 +127,8 @@ class MultiTargetAVHubertEncoderModel(ModelBase):
         self.eval()
 
     def half(self):
-        # common.fp16 (inference.py:155-156): the HIP path already computes with 16-bit operands; parameters stay fp32
+        # common.fp16 (inference.py:155-156): the HIP path computes with the operand type it was built with (16-bit by default;
+        # dtype=f32 / L2S_DTYPE=f32 is the reference's fp16=false precision); parameters stay fp32
         return self
 
     def reorder_encoder_out(self, encoder_out, new_order):

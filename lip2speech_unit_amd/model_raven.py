@@ -15,7 +15,7 @@ import torch.nn as nn
 from . import ops
 from .conformer import Conformer, ConformerConfig, Encoder
 from .conv3d_extractor import Conv3dResNet
-from .model import MultiTargetRAVENEncoderModelConfig, env_dtype
+from .model import MultiTargetRAVENEncoderModelConfig, env_dtype, refuse_f32
 from .model_auto_avsr import AutoAVSREncoder, MultiTargetAutoAVSREncoderModel
 from .plugin import cfg_get, register_model
 
@@ -58,6 +58,7 @@ class MultiTargetRAVENEncoderModel(MultiTargetAutoAVSREncoderModel):
     def build_model(cls, cfg=None, task=None, dtype=None, encoder_cfg: RAVENConfig = None,
                     conformer_cfg: ConformerConfig = None):
         dtype = env_dtype() if dtype is None else dtype
+        refuse_f32(dtype, "multi_target_raven")
         encoder_cfg = encoder_cfg or RAVENConfig.from_model_cfg(cfg)
         conformer_cfg = conformer_cfg or ConformerConfig.from_model_cfg(cfg)
         tgt_dict = getattr(task, "target_dictionary", None) if task is not None else None

@@ -10,11 +10,13 @@ from typing import Optional
 import torch
 
 from . import _lib
-from ._lib import (ACT_GELU, ACT_LRELU, ACT_NONE, ACT_PRELU, ACT_RELU, ACT_SWISH, ACT_TANH, BF16, F16, F_ACCUM,  # noqa: F401
+from ._lib import (ACT_GELU, ACT_LRELU, ACT_NONE, ACT_PRELU, ACT_RELU, ACT_SWISH, ACT_TANH, BF16, F16, F32, F_ACCUM,  # noqa: F401
                    F_DUAL, F_MASK, F_OUT_F32, F_RES_F32, F_RES_POST, F_RES_PRE, MODE_CONV1D, MODE_CONV2D,
                    MODE_LINEAR, GemmDesc, L2SError, check)
 
-_TORCH16 = {F16: torch.float16, BF16: torch.bfloat16}
+# operand / activation storage type of a dtype code (F32 = the fp32 reference-precision mode of stage 1)
+_TORCH16 = {F16: torch.float16, BF16: torch.bfloat16, F32: torch.float32}
+_DTYPE_NAME = {F16: "f16", BF16: "bf16", F32: "f32"}
 
 
 class KernelProfiler:
@@ -69,7 +71,9 @@ def dtype_code(t: torch.dtype) -> int:
         return F16
     if t == torch.bfloat16:
         return BF16
-    raise L2SError(f"unsupported 16-bit dtype {t}")
+    if t == torch.float32:
+        return F32
+    raise L2SError(f"unsupported operand dtype {t}")
 
 
 def _stream() -> int:
@@ -134,7 +138,7 @@ def tapgemm(A, W, C, *, M, N, Cin, ntaps=1, lda=None, ldc=None, bias=None, slope
         check(lib.l2s_tapgemm(ctypes.byref(d), _stream()), "l2s_tapgemm")
         return
     var = lib.l2s_tapgemm_variant(ctypes.byref(d))
-    key = f"tapgemm<{'f16' if dtype == F16 else 'bf16'},{var // 1000}x{var % 1000},mode{mode}>"
+    key = f"tapgemm<{_DTYPE_NAME[dtype]},{var // 1000 % 1000}x{var % 1000},mode{mode}>"   # (fp32: variant 2128128 -> 128x128)
     if _profiler is not None:  # one kernel instantiation per epilogue family: name it like rocprofv3 sees it
         fam = lib.l2s_tapgemm_epilogue_family(ctypes.byref(d))
         if var in (999064, 999128):  # patchconv.hip builds 5 of the 10 families; the others run on a superset
@@ -143,14 +147,15 @@ def tapgemm(A, W, C, *, M, N, Cin, ntaps=1, lda=None, ldc=None, bias=None, slope
     if _profiler is not None and _profiler.detail:
         key += f" M{M} N{N} Cin{Cin} taps{ntaps} g{groups} fl{flags:#x} act{act} alpha{alpha:g}"
     ktot = Cin * ntaps
-    esz = 4 if (flags & F_OUT_F32) else 2
+    osz = 4 if dtype == F32 else 2
+    esz = 4 if (flags & F_OUT_F32) else osz
     # algorithmic bytes: A once, W once, C written once; + the residual read, the second output, the accumulate read
     mn = float(M) * N * groups
-    nbytes = 2.0 * M * ktot * groups / max(ntaps, 1) + 2.0 * N * ktot * groups + esz * mn
+    nbytes = float(osz) * M * ktot * groups / max(ntaps, 1) + float(osz) * N * ktot * groups + esz * mn
     if R is not None:
-        nbytes += (4 if (flags & F_RES_F32) else 2) * mn
+        nbytes += (4 if (flags & F_RES_F32) else osz) * mn
     if flags & F_DUAL:
-        nbytes += 2 * mn
+        nbytes += osz * mn
     if flags & F_ACCUM:
         nbytes += esz * mn
     _run(key, lambda: lib.l2s_tapgemm(ctypes.byref(d), _stream()), kflops if kflops is not None else 2.0 * M * N * ktot * groups, nbytes,
@@ -335,7 +340,7 @@ def residual_linear(A, W, bias, x, *, M, N, K, dtype, alpha=1.0, cache=None, key
     slice-0-only bias of the split-K form are kept (a layer's dict of packed weights).
     ln = (gamma, beta, eps, y): the LayerNorm that follows the update, y = LayerNorm(x) (y may be x) - always applied; in the
     split-K form it rides in the reduction's launch."""
-    S = splitk_slices(M, N, K)
+    S = 0 if dtype == F32 else splitk_slices(M, N, K)   # fp32: one tap-GEMM with R = x in place, then l2s_layernorm
     if not S:
         tapgemm(A, W, x, M=M, N=N, Cin=K, bias=bias, alpha=alpha, R=x, ldr=N, flags=F_RES_POST, dtype=dtype)
         if ln is not None:

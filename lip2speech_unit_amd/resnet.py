@@ -190,7 +190,19 @@ class ResEncoder(nn.Module):
         dev = x.device
         N = B * T
         cur = torch.empty(N, 22, 22, 64, device=dev, dtype=t16)
-        if x.dtype == torch.uint8:
+        f32 = dt == ops.F32     # reference precision: the unfused stem and plain CONV2D tap-GEMMs (no resident / K-table forms)
+        if f32:
+            if x.dtype == torch.uint8:
+                crop, mean, std = self.u8_transform
+                xf = torch.empty(B, T, crop, crop, device=dev, dtype=torch.float32)
+                ops.preprocess_frames(x, xf, B=B, T=T, Hin=H, Win=W, crop=crop, mean=mean, std=std, dtype=dt)
+                x = xf
+            elif x.dtype != torch.float32:
+                x = x.float()
+            conv = torch.empty(N, 44, 44, 64, device=dev, dtype=t16)
+            ops.stem_conv3d(x, P["stem_w"], P["stem_b"], P["stem_s"], conv, B, T, dt)          # resnet.py:137-140
+            ops.maxpool2d_3x3s2(conv, cur, N, 44, 44, 64, dt)                                    # :141
+        elif x.dtype == torch.uint8:
             # raw decoder frames [B,T,Hin,Win]: centre crop + normalise (hubert_dataset.py:242-245) inside the stem's fetch
             crop, mean, std = self.u8_transform
             ops.stem_pool_fused_u8(x, P["stem_w"], P["stem_b"], P["stem_s"], cur, B, T, dt, crop=crop, mean=mean, std=std)
@@ -202,11 +214,11 @@ class ResEncoder(nn.Module):
         Hc = 22
 
         def resident(e):   # a BasicBlock the LDS-resident-image kernel takes (csrc/basicblock.hip): layer1 of ResNet-18
-            return (FUSED_BASICBLOCK and e["stride"] == 1 and e["cin"] == 64 and e["cout"] == 64 and "wd" not in e
+            return (not f32 and FUSED_BASICBLOCK and e["stride"] == 1 and e["cin"] == 64 and e["cout"] == 64 and "wd" not in e
                     and act == ACT_PRELU and (Hc + 2) * (Hc + 2) <= 576)
 
         def resident128(e):   # ... and the phase-staggered one of the 128-channel stage (csrc/basicblock_phase.hip): layer2, block 2
-            return (FUSED_BASICBLOCK128 and e["stride"] == 1 and e["cin"] == 128 and e["cout"] == 128 and "wd" not in e
+            return (not f32 and FUSED_BASICBLOCK128 and e["stride"] == 1 and e["cin"] == 128 and e["cout"] == 128 and "wd" not in e
                     and act == ACT_PRELU and Hc == 11)
 
         blocks = P["blocks"]
@@ -245,7 +257,7 @@ class ResEncoder(nn.Module):
                 # a 3x3 convolution of this block: on the small maps of layer3 / layer4 (image = one row of A) through the K-block
                 # table - every output position sums only its in-map taps - else as a CONV2D tap-GEMM
                 ho = (hin + 2 - 3) // st + 1
-                if (KTAB_CONV and act == ACT_PRELU and hin <= 11 and ho <= 6 and N >= 256 and N % 8 == 0 and ci % 64 == 0
+                if (not f32 and KTAB_CONV and act == ACT_PRELU and hin <= 11 and ho <= 6 and N >= 256 and N % 8 == 0 and ci % 64 == 0
                         and cout >= 256 and cout % 64 == 0):
                     key = ("ktab", tag)
                     if key not in e:
@@ -261,7 +273,7 @@ class ResEncoder(nn.Module):
                             flags=F_RES_PRE if res is not None else 0, dtype=dt)
 
             conv3x3(cur, e["w1"], e["b1"], e["s1"], h1, Hc, cin, s, 1)
-            if (FUSED_STAGE128_TAIL and FUSED_BASICBLOCK128 and "wa" in e and s == 2 and Ho == 11 and Hc == 22 and act == ACT_PRELU
+            if (not f32 and FUSED_STAGE128_TAIL and FUSED_BASICBLOCK128 and "wa" in e and s == 2 and Ho == 11 and Hc == 22 and act == ACT_PRELU
                     and bi < len(blocks) and blocks[bi]["stride"] == 1 and blocks[bi]["cin"] == 128 and blocks[bi]["cout"] == 128
                     and "wd" not in blocks[bi]):
                 # layer2 behind its first conv in ONE launch: conv2 of this block + the downsample as its residual, then the next block
