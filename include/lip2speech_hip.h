@@ -437,6 +437,31 @@ int l2s_resstage_fused(const void* xl, const void* const* w, const float* const*
 int l2s_preprocess_frames(const uint8_t* frames, void* y, int B, int T, int Hin, int Win, int crop, float mean,
                           float std, int dtype, void* stream);
 
+/*
+ * Log-mel analysis of waveforms, the vocoder's mel conditioning made from audio (create_dataset.py:62-75 extract_mel_spec with
+ * config.py:21-27: TacotronSTFT(640, 160, 640, 80, 16000, 0.0, 8000.0).mel_spectrogram; TacotronSTFT itself is third-party -
+ * fairseq's examples/.../tacotron2 - and not in the reference tree: an F.conv1d with a dense windowed Fourier basis in fp32,
+ * magnitude, a Slaney mel filterbank, log(clamp(., 1e-5))).  One launch, everything fp32 (a k-ordered fma chain per re / im):
+ *   wav: [B, S] samples with leading dimension ldw, fp32 in (-1, 1) or (wav_is_i16) int16 PCM taken as value / 32768;
+ *   n_samples: int32 [B] clip lengths (clamped to S), NULL = every clip has S samples;
+ *   mel: fp32 [B, T_rows, n_mels] time-major with row stride ldm (the .npy layout, and MelCodeGenerator's mel_rows).
+ * Each clip is analysed alone: clip b has T_b = 1 + n_b / hop frames, frame t covers samples [t*hop - n_fft/2, t*hop + n_fft/2)
+ * reflect-padded against n_b (never S); rows T_b <= t < T_rows are written as zeros, and a clip with n_b <= n_fft/2 (no valid
+ * reflect padding) has only zero rows.  Per frame: re/im[k] = sum_n x[n] basis, mag = sqrtf(re^2 + im^2),
+ * m[j] = sum_k fb[j][k] mag[k] (k ascending), out = logf(max(m, floor)).  The tables are data, built by the caller:
+ *   basis: fp32 [n_fft][n_fft], row n = sample of the frame, the analysis window folded in, 16-byte aligned.  Column c: tile
+ *     q = c / 32, lane l = c % 32, bin k = 32 (q / 2) + l; even q holds  w[n] cos(2 pi k n / n_fft), odd q holds
+ *     -w[n] sin(2 pi k n / n_fft) - except column 32 (q = 1, l = 0: the imaginary part of bin 0, identically zero), which holds
+ *     the real part of bin n_fft/2, w[n] cos(pi n).  Bins 0 and n_fft/2 are the real-only ones: n_fft columns in all, no padding.
+ *   fb: fp32 [n_mels][n_fft/2 + 1] dense filterbank; fb_range: int32 [n_mels][2] = [first, past-last) bin of each band's non-zero
+ *     weights (bins outside the range are not read; zeros inside it are harmless).
+ * Supported: n_fft = 640, hop = 160, n_mels = 80 (any window, filterbank and floor); other sizes return L2S_EUNSUPPORTED.
+ * B <= 65535, T_rows <= 2^22.  ldw >= S, ldm >= n_mels.
+ */
+int l2s_mel_spectrogram(const void* wav, int wav_is_i16, int64_t ldw, const int32_t* n_samples, int B, int S, const float* basis,
+                        const float* fb, const int32_t* fb_range, float* mel, int ldm, int T_rows, int n_fft, int hop,
+                        int n_mels, float floor_, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

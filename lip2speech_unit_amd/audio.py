@@ -1,0 +1,156 @@
+"""Log-mel analysis of waveforms on the device: the vocoder's mel conditioning made from audio.
+
+create_dataset.py:62-75 (extract_mel_spec) calls fairseq's tacotron2 `TacotronSTFT(...).mel_spectrogram(audio)` with the sizes
+of config.py:21-27; that class is third-party and not part of the reference tree.  Its recipe - reflect pad n_fft/2, periodic
+Hann window, a dense Fourier basis applied as F.conv1d in fp32, magnitude, Slaney mel filterbank, log(clamp(., 1e-5)) - is
+restated here as two fp32 tables built in numpy float64 (rounded once) and one HIP launch (csrc/melspec.hip).  There is no
+CPU path: host tensors raise L2SError like every other op.
+"""
+import numpy as np
+import torch
+
+from . import ops
+from ._lib import L2SError
+
+
+def _hz_to_mel(f):
+    """Slaney's auditory-toolbox scale: linear below 1 kHz (200/3 Hz per mel), logarithmic above (27 mels per factor 6.4)."""
+    f = np.asarray(f, dtype=np.float64)
+    lin = f / (200.0 / 3.0)
+    log = 15.0 + np.log(np.maximum(f, 1e-300) / 1000.0) / (np.log(6.4) / 27.0)
+    return np.where(f >= 1000.0, log, lin)
+
+
+def _mel_to_hz(m):
+    m = np.asarray(m, dtype=np.float64)
+    return np.where(m >= 15.0, 1000.0 * np.exp((np.log(6.4) / 27.0) * (m - 15.0)), (200.0 / 3.0) * m)
+
+
+def mel_filterbank(sr=16000, n_fft=640, n_mels=80, fmin=0.0, fmax=8000.0):
+    """Triangular filters on the Slaney scale, each normalised to unit area (`norm='slaney'`): float64 [n_mels, n_fft/2 + 1]."""
+    freqs = np.linspace(0.0, sr / 2.0, n_fft // 2 + 1)
+    edges = _mel_to_hz(np.linspace(_hz_to_mel(fmin), _hz_to_mel(fmax), n_mels + 2))
+    width = np.diff(edges)
+    ramps = edges[:, None] - freqs[None, :]
+    lower = -ramps[:-2] / width[:-1, None]
+    upper = ramps[2:] / width[1:, None]
+    fb = np.maximum(0.0, np.minimum(lower, upper))
+    return fb * (2.0 / (edges[2:] - edges[:-2]))[:, None]
+
+
+def hann_periodic(n):
+    return 0.5 - 0.5 * np.cos(2.0 * np.pi * np.arange(n) / n)
+
+
+def packed_basis(n_fft=640, window=None):
+    """The windowed real DFT as the [n_fft, n_fft] matrix of l2s_mel_spectrogram (include/lip2speech_hip.h): row = sample,
+    column c -> tile q = c // 32, lane l = c % 32, bin k = 32 (q // 2) + l; even tiles hold w cos, odd tiles -w sin, and
+    column 32 (the imaginary part of bin 0) holds the real part of bin n_fft/2.  float64."""
+    if n_fft % 64:
+        raise ValueError("n_fft must be a multiple of 64")
+    w = hann_periodic(n_fft) if window is None else np.asarray(window, dtype=np.float64)
+    n = np.arange(n_fft)
+    c = np.arange(n_fft)
+    q, lane = c // 32, c % 32
+    k = 32 * (q // 2) + lane
+    ang = 2.0 * np.pi * ((n[:, None] * k[None, :]) % n_fft) / n_fft     # the exact integer phase, reduced before the division
+    basis = np.where((q % 2 == 0)[None, :], np.cos(ang), -np.sin(ang))
+    basis[:, 32] = np.cos(np.pi * n)
+    return basis * w[:, None]
+
+
+def unpack_spectrum(y, n_fft=640):
+    """(re, im) [..., n_fft/2 + 1] of a product x @ packed_basis [..., n_fft] - the column map read backwards."""
+    y = np.asarray(y)
+    t = y.reshape(y.shape[:-1] + (n_fft // 64, 2, 32))
+    re = np.concatenate([t[..., 0, :].reshape(y.shape[:-1] + (n_fft // 2,)), y[..., 32:33]], axis=-1)
+    im = np.concatenate([t[..., 1, :].reshape(y.shape[:-1] + (n_fft // 2,)), np.zeros_like(y[..., :1])], axis=-1).copy()
+    im[..., 0] = 0.0
+    return re, im
+
+
+def num_frames(n_samples, hop=160):
+    return 1 + n_samples // hop
+
+
+class TacotronSTFT:
+    """`TacotronSTFT(...).mel_spectrogram(audio)` of extract_mel_spec, on the device; defaults from config.py:21-27."""
+
+    def __init__(self, filter_length=640, hop_length=160, win_length=640, n_mel_channels=80, sampling_rate=16000, mel_fmin=0.0,
+                 mel_fmax=8000.0, floor=1e-5):
+        if win_length != filter_length:
+            raise ValueError("win_length must equal filter_length")
+        self.n_fft, self.hop, self.n_mels, self.sr, self.floor = filter_length, hop_length, n_mel_channels, sampling_rate, floor
+        self.basis = packed_basis(filter_length).astype(np.float32)
+        fb = mel_filterbank(sampling_rate, filter_length, n_mel_channels, mel_fmin, mel_fmax)
+        self.fb = fb.astype(np.float32)
+        nbin = filter_length // 2 + 1
+        nz = self.fb != 0
+        self.fb_range = np.stack([np.where(nz.any(1), nz.argmax(1), 0),
+                                  np.where(nz.any(1), nbin - nz[:, ::-1].argmax(1), 0)], axis=1).astype(np.int32)
+        self._dev = {}
+
+    def tables(self, device):
+        """(basis, fb, fb_range) on `device`, uploaded once per device."""
+        device = torch.device(device)
+        if device.type != "cuda":
+            raise L2SError("mel analysis needs a HIP device (there is no CPU path)")
+        key = device.index if device.index is not None else torch.cuda.current_device()
+        if key not in self._dev:
+            self._dev[key] = tuple(torch.from_numpy(t).to(device) for t in (self.basis, self.fb, self.fb_range))
+        return self._dev[key]
+
+    def mel_rows(self, wav, n_samples=None):
+        """wav: device tensor [B, S], fp32 in (-1, 1) or int16 PCM.  n_samples: clip lengths - None (all S), a host sequence
+        (checked: n_fft/2 < n <= S) or an int32 device tensor (not read on the host; a clip of <= n_fft/2 samples gives zero rows).
+        Returns fp32 [B, 1 + S // hop, n_mel]; clip b's rows past 1 + n_b // hop are zeros."""
+        if not isinstance(wav, torch.Tensor) or not wav.is_cuda:
+            raise L2SError("mel_rows: expected a device tensor (there is no CPU path)")
+        if wav.dim() != 2:
+            raise ValueError("wav: [B, S]")
+        B, S = wav.shape
+        if wav.stride(1) != 1:
+            wav = wav.contiguous()
+        if n_samples is None:
+            if S <= self.n_fft // 2:
+                raise ValueError(f"reflect padding needs more than {self.n_fft // 2} samples, got {S}")
+        elif isinstance(n_samples, torch.Tensor) and n_samples.is_cuda:
+            if n_samples.dtype != torch.int32 or n_samples.shape != (B,):
+                raise ValueError("n_samples: int32 [B]")
+            n_samples = n_samples.contiguous()
+        else:
+            ns = [int(v) for v in (n_samples.tolist() if hasattr(n_samples, "tolist") else n_samples)]
+            if len(ns) != B:
+                raise ValueError("n_samples: one length per clip")
+            if any(v <= self.n_fft // 2 or v > S for v in ns):
+                raise ValueError(f"n_samples: every clip needs {self.n_fft // 2} < n <= {S} samples, got {ns}")
+            n_samples = torch.tensor(ns, dtype=torch.int32).to(wav.device)
+        basis, fb, fb_range = self.tables(wav.device)
+        T = num_frames(S, self.hop)
+        mel = torch.empty(B, T, self.n_mels, device=wav.device, dtype=torch.float32)
+        ops.mel_spectrogram(wav, mel, basis, fb, fb_range, B=B, S=S, T_rows=T, n_samples=n_samples, ldw=wav.stride(0) if B > 1 else S,
+                            n_fft=self.n_fft, hop=self.hop, n_mels=self.n_mels, floor=self.floor)
+        return mel
+
+    def mel_spectrogram(self, audio):
+        """audio [B, S] in (-1, 1) -> [B, n_mel, T], the call extract_mel_spec makes."""
+        return self.mel_rows(audio).transpose(1, 2)
+
+
+_default = None
+
+
+def default_stft():
+    global _default
+    if _default is None:
+        _default = TacotronSTFT()
+    return _default
+
+
+def read_wav_s16(path, sampling_rate=16000):
+    """int16 PCM of a 16 kHz mono s16 wav (stdlib `wave`; anything else is refused)."""
+    import wave
+    with wave.open(path, "rb") as w:
+        if w.getnchannels() != 1 or w.getsampwidth() != 2 or w.getframerate() != sampling_rate or w.getcomptype() != "NONE":
+            raise ValueError(f"{path}: expected {sampling_rate} Hz mono s16 PCM")
+        return np.frombuffer(w.readframes(w.getnframes()), dtype="<i2").astype(np.int16)

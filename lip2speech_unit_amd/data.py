@@ -216,8 +216,12 @@ def audio_num_samples(path, pad=None):
 
 
 class MelCodeDataset:
-    def __init__(self, file_list, code_hop_size=320, mel_hop_size=160, code_dict_path=None, pad=None):
+    def __init__(self, file_list, code_hop_size=320, mel_hop_size=160, code_dict_path=None, pad=None, mel_from_audio=False,
+                 stft=None):
+        """mel_from_audio: the mel/ directory is not touched - the wav is read, zero-extended to the padded length and analysed
+        on the device (audio.TacotronSTFT, or `stft`: anything with its mel_rows) before the same trimming rule applies."""
         self.audio_files, self.mel_files, self.codes = file_list[:3]
+        self.mel_from_audio, self.stft = mel_from_audio, stft
         self.t_labels = file_list[3] if len(file_list) > 3 else None   # text supervision (dataset_multi_input.py:225-239)
         self.code_hop_size, self.mel_hop_size, self.pad = code_hop_size, mel_hop_size, pad
         self.code_dict = load_code_dict(code_dict_path)
@@ -225,6 +229,19 @@ class MelCodeDataset:
 
     def __len__(self):
         return len(self.audio_files)
+
+    def analyse(self, filename, n_audio):
+        """[T, n_mel] log-mel of the wav, zero-extended to n_audio samples (what --pad does to the length)."""
+        import torch
+        from . import audio
+        stft = self.stft if self.stft is not None else audio.default_stft()
+        pcm = audio.read_wav_s16(filename)
+        wav = np.zeros(n_audio, np.int16)
+        wav[: pcm.shape[0]] = pcm[:n_audio]
+        wav = torch.from_numpy(wav).unsqueeze(0)
+        if self.stft is None:
+            wav = wav.cuda()
+        return np.asarray(stft.mel_rows(wav)[0].cpu())
 
     def __getitem__(self, index):
         """dataset_multi_input.py:198-291 with segment_size=-1: (feats{code,mel,spkr[,t_label]}, None, filename, None)."""
@@ -237,7 +254,7 @@ class MelCodeDataset:
         if self.t_labels is not None:
             t_label = np.asarray(self.t_labels[index], dtype=np.int64)[:code_length]
             assert t_label.shape[0] == code.shape[0], f"{filename}: {t_label.shape[0]} != {code.shape[0]}"
-        mel = np.load(self.mel_files[index])
+        mel = self.analyse(filename, n_audio) if self.mel_from_audio else np.load(self.mel_files[index])
         mel_length = min(n_audio // self.mel_hop_size, mel.shape[0])
         mel = mel[:mel_length]
         cut = min(mel_length * self.mel_hop_size, code_length * self.code_hop_size)

@@ -529,6 +529,23 @@ def preprocess_frames(frames, y, *, B, T, Hin, Win, crop=88, mean=0.421, std=0.1
     _run("l2s_preprocess_frames", lambda: _lib.load().l2s_preprocess_frames(_ptr(frames), _ptr(y), B, T, Hin, Win, crop, mean, std, dtype, _stream()))
 
 
+def mel_spectrogram(wav, mel, basis, fb, fb_range, *, B, S, T_rows, n_samples=None, ldw=None, ldm=None, n_fft=640, hop=160, n_mels=80,
+                    floor=1e-5):
+    """Log-mel analysis in one launch (csrc/melspec.hip; audio.TacotronSTFT builds the tables): wav fp32 or int16 [B, S] ->
+    mel fp32 [B, T_rows, n_mels], every clip analysed alone against n_samples[b] (int32 device tensor; None = S)."""
+    if wav.dtype not in (torch.float32, torch.int16):
+        raise L2SError(f"wav: expected float32 or int16, got {wav.dtype}")
+    if n_samples is not None and n_samples.dtype != torch.int32:
+        raise L2SError("n_samples must be int32")
+    _req(wav, None, "wav"), _req(mel, torch.float32, "mel"), _req(basis, torch.float32, "basis"), _req(fb, torch.float32, "fb")
+    _req(fb_range, torch.int32, "fb_range")
+    frames = float(B) * T_rows
+    _run("l2s_mel_spectrogram", lambda: _lib.load().l2s_mel_spectrogram(
+        _ptr(wav), int(wav.dtype == torch.int16), ldw if ldw is not None else S, _ptr(n_samples), B, S, _ptr(basis), _ptr(fb),
+        _ptr(fb_range), _ptr(mel), ldm if ldm is not None else n_mels, T_rows, n_fft, hop, n_mels, float(floor), _stream()),
+        flops=2.0 * frames * n_fft * n_fft, nbytes=float(B) * S * wav.element_size() + 4.0 * frames * n_mels + 4.0 * n_fft * n_fft)
+
+
 # ---- torch.library registration ("PyTorch-ROCm custom ops", SURVEY 8b last row) --------------------------------------------------
 # Every launcher above is ALSO a dispatcher-visible operator `torch.ops.lip2speech.<name>` (schema below, CUDA = HIP kernel only: a
 # CPU tensor finds no kernel and raises; a fake / meta implementation gives shapes to torch.compile and fake-tensor tracing), and
@@ -609,6 +626,9 @@ _SCHEMAS = {
                      "int[] dils, float slope, Tensor? lens=None, int len_mul=1, int dtype=0) -> ()",
     "preprocess_frames": "(Tensor frames, Tensor(a!) y, *, int B, int T, int Hin, int Win, int crop=88, float mean=0.421, "
                          "float std=0.165, int dtype=0) -> ()",
+    "mel_spectrogram": "(Tensor wav, Tensor(a!) mel, Tensor basis, Tensor fb, Tensor fb_range, *, int B, int S, int T_rows, "
+                       "Tensor? n_samples=None, int? ldw=None, int? ldm=None, int n_fft=640, int hop=160, int n_mels=80, "
+                       "float floor=1e-05) -> ()",
 }
 # C-ABI entry each operator launches (tests/test_torchlib_cpu.py: every device entry of include/lip2speech_hip.h has a twin)
 ENTRY_OF = {n: "l2s_" + n for n in _SCHEMAS}

@@ -2,7 +2,8 @@
 """Stage-2 CLI — mirrors multi_input_vocoder/inference.py:167-259 (argparse surface :170-180, worker :85-165).
 
   python -m lip2speech_unit_amd.vocoder_inference <config.json> <label/test.tsv> <dict.unt.txt> \
-      --output_dir D --checkpoint_file C -n -1 [--pad N] [--synthetic_weights]
+      --output_dir D --checkpoint_file C -n -1 [--pad N] [--synthetic_weights] [--mel_from_audio]
+--mel_from_audio: the mel conditioning is analysed from audio/*.wav on the device (audio.TacotronSTFT); mel/ is not read.
 Writes D/pred_wav/<spk>/<utt>.wav (int16, 16 kHz) like :157-165.
 """
 import argparse
@@ -32,6 +33,7 @@ def main(argv=None):
     p.add_argument("-n", type=int, default=10)
     p.add_argument("--synthetic_weights", action="store_true")
     p.add_argument("--dtype", default="f16", choices=["f16", "bf16"])
+    p.add_argument("--mel_from_audio", action="store_true")
     a = p.parse_args(argv)
     if a.code_file is not None:
         raise NotImplementedError("--code_file (units without mel/speaker) is not the multi-input path")
@@ -49,7 +51,7 @@ def main(argv=None):
     gen.cuda().eval()
     gen.remove_weight_norm()                                                                   # :142-143
     ds = MelCodeDataset(parse_manifest(a.input_code_file), h.code_hop_size, h.mel_hop_size, code_dict_path=a.code_dict_path,
-                        pad=a.pad)
+                        pad=a.pad, mel_from_audio=a.mel_from_audio)
     os.makedirs(a.output_dir, exist_ok=True)
     n = len(ds) if a.n == -1 else min(a.n, len(ds))
     audio_s, wall = 0.0, 0.0
