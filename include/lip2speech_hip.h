@@ -462,6 +462,48 @@ int l2s_mel_spectrogram(const void* wav, int wav_is_i16, int64_t ldw, const int3
                         const float* fb, const int32_t* fb_range, float* mel, int ldm, int T_rows, int n_fft, int hop,
                         int n_mels, float floor_, void* stream);
 
+/*
+ * Forward (scoring) half of the `multi_target` criterion (multi_target_lip2speech/criterion.py), csrc/criterion.hip.  All three
+ * entries write PER-CLIP results that depend on that clip's rows alone (no atomics, fixed reduction order: the same bytes for a
+ * clip whatever its batch mates and from run to run); batch totals are the caller's sum over clips in index order.  Terms are
+ * evaluated in fp32, sums across lanes / rows / frames are carried in fp64 and rounded to fp32 once.  lens: int32 [B] or NULL.
+ *
+ * l2s_unit_ce - label-smoothed cross-entropy and accuracy over the unit logits (criterion.py:148-161 get_lprobs_and_target with
+ * fairseq's label_smoothed_nll_loss / compute_accuracy, which are not in the reference tree), without writing log-probabilities:
+ *   logits: fp32 rows (b, t), row (b*T2 + t) at logits + row*ldl, V <= 4096 classes; target: int32 [B, ldt].
+ * A row counts when t < min(T2, ldt) (:151-152), target != pad_idx and t < lens[b]*len_mul (the clip-alone rule: a label
+ * past the clip's own frames never scores logits computed from padding).  Per clip over its counted rows:
+ *   nll = sum -lprob[target], smooth = sum_t sum_v -lprob[v] (= V*lse - sum_v logit), n_correct = #(argmax == target, first
+ *   index on ties), n_tok = #rows.   loss = (1 - eps - eps/(V-1)) nll + eps/(V-1) smooth is the caller's.
+ * ignore_prefix must be 0 (:154-160 is not built): anything else returns L2S_EUNSUPPORTED.  A target outside [0, V) is not counted.
+ */
+int l2s_unit_ce(const float* logits, int ldl, const int32_t* target, int ldt, const int32_t* lens, int len_mul, int B, int T2,
+                int V, int pad_idx, int ignore_prefix, float* nll, float* smooth, int32_t* n_correct, int32_t* n_tok,
+                void* stream);
+/*
+ * l2s_mel_l1_sc - the sums behind the masked L1 and spectral-convergence terms (criterion.py:63-89 and :189-201):
+ *   pred: fp32 [B, Tm_pred, n_mels] (the conformer's [B*2T, 160] rows viewed 80 wide), targ: fp32 [B, Tm_targ, n_mels] zero-padded,
+ *   both dense.  Per clip over rows t < min(lens[b]*len_mul, crop_len, Tm_pred, Tm_targ)  (len_mul = 4; crop_len as at :67):
+ *   l1 = sum |p - t|, sq = sum (p - t)^2, tsq = sum t^2, n_rows = the row count.
+ * The caller forms  l1 / n_mels [/ n_rows]  and  sqrt(sq) / sqrt(tsq) [* n_rows]  (:78-82, :199-200).
+ */
+int l2s_mel_l1_sc(const float* pred, int Tm_pred, const float* targ, int Tm_targ, const int32_t* lens, int len_mul, int B,
+                  int n_mels, int crop_len, float* l1, float* sq, float* tsq, int32_t* n_rows, void* stream);
+/*
+ * l2s_ctc_loss - torch.nn.CTCLoss(blank, zero_infinity=True) forward per clip (criterion.py:45,103-112) straight from logits:
+ *   logits: fp32 rows (b, t) of L frames per clip, V <= 4096; clip b uses its first min(lens[b]*len_mul, L) frames;
+ *   targets: int32 concatenated labels, clip b's are targets[tgt_offs[b] .. + tgt_lens[b]); S_max >= every tgt_lens[b], <= 511.
+ *   nll: fp32 [B] = -log p(labels | frames), 0 where that is infinite (no alignment: more labels, counting a blank between
+ *   repeats, than frames) and for a clip without frames.  A clip with tgt_lens[b] > S_max or a label outside [0, V) gets NaN.
+ * Two launches: every frame's log-sum-exp and the log-probabilities of the blank and the clip's labels go to the compact
+ * workspace [B, L, S_max + 1] fp32; one workgroup per clip then runs the alpha recursion over the 2S+1 extended labels.
+ * l2s_ctc_loss_workspace gives the bytes needed, 0 for an unsupported size (S_max > 511); such a call returns L2S_EUNSUPPORTED.
+ */
+size_t l2s_ctc_loss_workspace(int B, int L, int S_max);
+int l2s_ctc_loss(const float* logits, int ldl, const int32_t* lens, int len_mul, int B, int L, int V, int blank,
+                 const int32_t* targets, const int32_t* tgt_lens, const int32_t* tgt_offs, int S_max, void* workspace,
+                 size_t workspace_bytes, float* nll, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

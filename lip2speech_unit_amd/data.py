@@ -60,7 +60,7 @@ class MultiTargetDataset(DatasetBase):
     (inference.py:164-179) can batch it: `num_tokens` / `size` / `ordered_indices` follow hubert_dataset.py:533-552."""
 
     def __init__(self, manifest_path, label_path=None, label_processor=None, pad=1, image_mean=0.421, image_std=0.165,
-                 image_crop_size=88):
+                 image_crop_size=88, text_label_path=None):
         with open(manifest_path) as f:
             self.root = f.readline().strip()
             rows = [ln.rstrip("\n").split("\t") for ln in f if ln.strip()]
@@ -73,6 +73,12 @@ class MultiTargetDataset(DatasetBase):
             with open(label_path) as f:
                 self.labels = [ln.rstrip("\n") for ln in f]
             assert len(self.labels) == len(rows), "label file and manifest disagree"
+        # text supervision (dataset.py:236-238): one line of space-separated piece ids per clip, tokenised beforehand
+        self.text_labels = None
+        if text_label_path is not None and os.path.exists(text_label_path):
+            with open(text_label_path) as f:
+                self.text_labels = [np.asarray([int(x) for x in ln.split()], dtype=np.int64) for ln in f.read().splitlines()]
+            assert len(self.text_labels) == len(rows), "text label file and manifest disagree"
         self.label_processor = label_processor
         self.label_processors = [label_processor]
         self.pad = pad
@@ -107,6 +113,8 @@ class MultiTargetDataset(DatasetBase):
             if not os.path.exists(p):
                 raise FileNotFoundError(f"{p} does not exist")
             sample[kind] = torch.from_numpy(np.load(p).astype(np.float32))
+        if self.text_labels is not None:
+            sample["text_labels"] = torch.from_numpy(self.text_labels[index])
         return sample
 
     def collater(self, samples: List[dict]):
@@ -138,6 +146,9 @@ class MultiTargetDataset(DatasetBase):
             batch["target"] = None
         mlen = max(len(s["mel"]) for s in samples)
         batch["mel"] = torch.stack([torch.nn.functional.pad(s["mel"], [0, 0, 0, mlen - len(s["mel"])]) for s in samples])
+        if "text_labels" in samples[0]:                                   # dataset.py:250-255: 1-D, no padding
+            batch["text_labels"] = torch.cat([s["text_labels"] for s in samples]).int()
+            batch["text_labels_lengths"] = torch.tensor([s["text_labels"].shape[0] for s in samples], dtype=torch.int32)
         return batch
 
 

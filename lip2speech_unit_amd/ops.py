@@ -98,6 +98,13 @@ def _req(t: torch.Tensor, dtype=None, name="tensor"):
     return t
 
 
+def _extent(t: torch.Tensor) -> int:
+    """Elements addressable from t's first element inside its own view (what a kernel may touch through t.data_ptr())."""
+    if t.numel() == 0:
+        return 0
+    return 1 + sum((n - 1) * st for n, st in zip(t.shape, t.stride()))
+
+
 def tapgemm(A, W, C, *, M, N, Cin, ntaps=1, lda=None, ldc=None, bias=None, slope=None, R=None, ldr=None, C2=None,
             ldc2=None, lens=None, mode=MODE_LINEAR, T_out=0, T_in=0, stride=1, dil=1, off=0, Ho=0, Wo=0, Hi=0, Wi=0,
             KW=1, pad=0, out_row_mul=1, out_row_add=0, mask_T=0, mask_mul=1, act=ACT_NONE, flags=0, dtype=F16,
@@ -546,6 +553,75 @@ def mel_spectrogram(wav, mel, basis, fb, fb_range, *, B, S, T_rows, n_samples=No
         flops=2.0 * frames * n_fft * n_fft, nbytes=float(B) * S * wav.element_size() + 4.0 * frames * n_mels + 4.0 * n_fft * n_fft)
 
 
+def unit_ce(logits, target, nll, smooth, n_correct, n_tok, *, B, T2, V, ldl=None, ldt=None, lens=None, len_mul=2, pad_idx=1,
+            ignore_prefix=0):
+    """Label-smoothed cross-entropy sums and accuracy counts per clip in one pass over fp32 logits [B*T2, ldl] (csrc/criterion.hip):
+    target int32 [B, ldt]; outputs nll / smooth fp32 [B], n_correct / n_tok int32 [B].  A row counts when t < min(T2, ldt),
+    target != pad_idx and t < lens[b]*len_mul."""
+    _req(logits, torch.float32, "logits"), _req(target, torch.int32, "target"), _req(nll, torch.float32, "nll")
+    _req(smooth, torch.float32, "smooth"), _req(n_correct, torch.int32, "n_correct"), _req(n_tok, torch.int32, "n_tok")
+    if lens is not None:
+        _req(lens, torch.int32, "lens")
+    ldl = ldl if ldl is not None else V
+    ldt = ldt if ldt is not None else target.stride(0)
+    if min(nll.numel(), smooth.numel(), n_correct.numel(), n_tok.numel()) < B or (lens is not None and lens.numel() < B):
+        raise L2SError("unit_ce: per-clip tensors shorter than B")
+    if (B * T2 - 1) * ldl + V > _extent(logits):
+        raise L2SError("unit_ce: logits smaller than B*T2 rows of ldl")
+    if (B - 1) * ldt + min(T2, ldt) > _extent(target):
+        raise L2SError("unit_ce: target smaller than [B, ldt]")
+    _run("l2s_unit_ce", lambda: _lib.load().l2s_unit_ce(
+        _ptr(logits), ldl, _ptr(target), ldt, _ptr(lens), len_mul, B, T2, V, pad_idx, ignore_prefix, _ptr(nll), _ptr(smooth),
+        _ptr(n_correct), _ptr(n_tok), _stream()), nbytes=4.0 * B * T2 * V)
+
+
+def mel_l1_sc(pred, targ, l1, sq, tsq, n_rows, *, B, Tm_pred, Tm_targ, crop_len, lens=None, len_mul=4, n_mels=80):
+    """Masked L1 / spectral-convergence sums per clip (csrc/criterion.hip): pred fp32 [B, Tm_pred, n_mels], targ fp32
+    [B, Tm_targ, n_mels], both dense; over rows t < min(lens[b]*len_mul, crop_len, Tm_pred, Tm_targ): l1 = sum|p-t|,
+    sq = sum (p-t)^2, tsq = sum t^2 (fp32 [B]) and n_rows int32 [B]."""
+    _req(pred, torch.float32, "pred"), _req(targ, torch.float32, "targ")
+    for t, n in ((l1, "l1"), (sq, "sq"), (tsq, "tsq")):
+        _req(t, torch.float32, n)
+    _req(n_rows, torch.int32, "n_rows")
+    if lens is not None:
+        _req(lens, torch.int32, "lens")
+    if not pred.is_contiguous() or not targ.is_contiguous():
+        raise L2SError("mel_l1_sc: pred and targ must be dense")
+    if pred.numel() < B * Tm_pred * n_mels or targ.numel() < B * Tm_targ * n_mels:
+        raise L2SError("mel_l1_sc: pred / targ smaller than [B, Tm, n_mels]")
+    if min(l1.numel(), sq.numel(), tsq.numel(), n_rows.numel()) < B or (lens is not None and lens.numel() < B):
+        raise L2SError("mel_l1_sc: per-clip tensors shorter than B")
+    _run("l2s_mel_l1_sc", lambda: _lib.load().l2s_mel_l1_sc(
+        _ptr(pred), Tm_pred, _ptr(targ), Tm_targ, _ptr(lens), len_mul, B, n_mels, crop_len, _ptr(l1), _ptr(sq), _ptr(tsq),
+        _ptr(n_rows), _stream()), nbytes=8.0 * B * min(Tm_pred, Tm_targ) * n_mels)
+
+
+def ctc_loss_workspace_bytes(B, L, S_max):
+    n = _lib.load().l2s_ctc_loss_workspace(B, L, S_max)
+    if n == 0:
+        raise L2SError(f"l2s_ctc_loss_workspace: unsupported size (B={B}, L={L}, S_max={S_max}; at most 511 labels per clip)")
+    return n
+
+
+def ctc_loss(logits, targets, tgt_lens, tgt_offs, workspace, nll, *, B, L, V, S_max, blank=0, ldl=None, lens=None, len_mul=2):
+    """torch.nn.CTCLoss(blank, zero_infinity=True) forward per clip from fp32 logits [B*L, ldl] (csrc/criterion.hip): targets
+    int32 concatenated, clip b's labels at tgt_offs[b] .. + tgt_lens[b] (int32 [B] each, <= S_max); clip b uses
+    min(lens[b]*len_mul, L) frames; nll fp32 [B].  workspace: ctc_loss_workspace_bytes(B, L, S_max) bytes."""
+    _req(logits, torch.float32, "logits"), _req(targets, torch.int32, "targets"), _req(tgt_lens, torch.int32, "tgt_lens")
+    _req(tgt_offs, torch.int32, "tgt_offs"), _req(nll, torch.float32, "nll")
+    if lens is not None:
+        _req(lens, torch.int32, "lens")
+    ldl = ldl if ldl is not None else V
+    if (B * L - 1) * ldl + V > _extent(logits):
+        raise L2SError("ctc_loss: logits smaller than B*L rows of ldl")
+    if min(tgt_lens.numel(), tgt_offs.numel(), nll.numel()) < B or (lens is not None and lens.numel() < B):
+        raise L2SError("ctc_loss: per-clip tensors shorter than B")
+    _run("l2s_ctc_loss", lambda: _lib.load().l2s_ctc_loss(
+        _ptr(logits), ldl, _ptr(lens), len_mul, B, L, V, blank, _ptr(targets) if targets.numel() else None, _ptr(tgt_lens),
+        _ptr(tgt_offs), S_max, _ptr(workspace), workspace.numel() * workspace.element_size(), _ptr(nll), _stream()),
+        nbytes=4.0 * B * L * V)
+
+
 # ---- torch.library registration ("PyTorch-ROCm custom ops", SURVEY 8b last row) --------------------------------------------------
 # Every launcher above is ALSO a dispatcher-visible operator `torch.ops.lip2speech.<name>` (schema below, CUDA = HIP kernel only: a
 # CPU tensor finds no kernel and raises; a fake / meta implementation gives shapes to torch.compile and fake-tensor tracing), and
@@ -629,13 +705,20 @@ _SCHEMAS = {
     "mel_spectrogram": "(Tensor wav, Tensor(a!) mel, Tensor basis, Tensor fb, Tensor fb_range, *, int B, int S, int T_rows, "
                        "Tensor? n_samples=None, int? ldw=None, int? ldm=None, int n_fft=640, int hop=160, int n_mels=80, "
                        "float floor=1e-05) -> ()",
+    "unit_ce": "(Tensor logits, Tensor target, Tensor(a!) nll, Tensor(b!) smooth, Tensor(c!) n_correct, Tensor(d!) n_tok, *, int B, "
+               "int T2, int V, int? ldl=None, int? ldt=None, Tensor? lens=None, int len_mul=2, int pad_idx=1, "
+               "int ignore_prefix=0) -> ()",
+    "mel_l1_sc": "(Tensor pred, Tensor targ, Tensor(a!) l1, Tensor(b!) sq, Tensor(c!) tsq, Tensor(d!) n_rows, *, int B, int Tm_pred, "
+                 "int Tm_targ, int crop_len, Tensor? lens=None, int len_mul=4, int n_mels=80) -> ()",
+    "ctc_loss": "(Tensor logits, Tensor targets, Tensor tgt_lens, Tensor tgt_offs, Tensor(a!) workspace, Tensor(b!) nll, *, int B, "
+                "int L, int V, int S_max, int blank=0, int? ldl=None, Tensor? lens=None, int len_mul=2) -> ()",
 }
 # C-ABI entry each operator launches (tests/test_torchlib_cpu.py: every device entry of include/lip2speech_hip.h has a twin)
 ENTRY_OF = {n: "l2s_" + n for n in _SCHEMAS}
 ENTRY_OF.update({"maxpool2d_3x3s2": "l2s_maxpool2d_3x3s2", "avgpool_hw": "l2s_avgpool_hw"})
 # host-side queries of the ABI (no launch, nothing for the dispatcher to see)
 HOST_QUERIES = ("l2s_abi_version", "l2s_build_info", "l2s_tapgemm_variant", "l2s_tapgemm_epilogue_family", "l2s_beam_decode_workspace",
-                "l2s_ctc_beam_workspace")
+                "l2s_ctc_beam_workspace", "l2s_ctc_loss_workspace")
 # SURVEY 8(b)'s operator names -> the entry that implements them (`mel_head` is a composition of linear_epilogue launches,
 # conformer.py::Conformer.forward_rows; it has no kernel of its own)
 ALIASES = {"frontend3d_stem": "stem_pool_fused", "resnet_trunk": "basiclayer_fused", "linear_epilogue": "tapgemm",

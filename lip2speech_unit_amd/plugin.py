@@ -6,7 +6,8 @@ fairseq's decorators refuse a class that does not extend `FairseqTask` / `BaseFa
 not extend `FairseqDataclass` (ValueError), so the bases are chosen HERE, once, at import time:
 
 * fairseq importable  -> TaskBase = FairseqTask, ModelBase = BaseFairseqModel, DataclassBase = FairseqDataclass,
-  DatasetBase = FairseqDataset, and `register_task` / `register_model` below forward to fairseq's decorators.  Any error
+  DatasetBase = FairseqDataset, CriterionBase = FairseqCriterion, and `register_task` / `register_model` /
+  `register_criterion` below forward to fairseq's decorators.  Any error
   they raise propagates: a plugin that cannot register must not look loaded.
 * fairseq absent (this build image: it is an un-vendored dependency of the reference) -> small stand-alone bases with the
   same constructor signatures, and the decorators only fill the local registries.
@@ -27,8 +28,11 @@ logger = logging.getLogger(__name__)
 
 TASK_REGISTRY = {}    # name -> (class, config dataclass)
 MODEL_REGISTRY = {}   # name -> (class, config dataclass)
+CRITERION_REGISTRY = {}   # name -> (class, config dataclass)
 
 try:
+    from fairseq.criterions import FairseqCriterion as CriterionBase
+    from fairseq.criterions import register_criterion as _fairseq_register_criterion
     from fairseq.data import FairseqDataset as DatasetBase
     from fairseq.dataclass import FairseqDataclass as DataclassBase
     from fairseq.models import BaseFairseqModel as ModelBase
@@ -38,7 +42,7 @@ try:
     HAVE_FAIRSEQ = True
 except ImportError:
     HAVE_FAIRSEQ = False
-    _fairseq_register_model = _fairseq_register_task = None
+    _fairseq_register_model = _fairseq_register_task = _fairseq_register_criterion = None
 
     @dataclass
     class DataclassBase:
@@ -64,6 +68,30 @@ except ImportError:
 
     class DatasetBase(torch.utils.data.Dataset):
         pass
+
+    class CriterionBase(nn.Module):
+        """FairseqCriterion: an nn.Module built from `task`; `build_criterion` fills the constructor from the config's fields."""
+
+        def __init__(self, task):
+            super().__init__()
+            self.task = task
+            tgt = getattr(task, "target_dictionary", None)
+            self.padding_idx = tgt.pad() if tgt is not None else -100
+
+        @classmethod
+        def build_criterion(cls, cfg, task):
+            import inspect
+            init_args = {}
+            for p in inspect.signature(cls).parameters.values():
+                if p.name == "task":
+                    init_args["task"] = task
+                elif p.name == "cfg":
+                    init_args["cfg"] = cfg
+                elif cfg_get(cfg, p.name, None) is not None:
+                    init_args[p.name] = cfg_get(cfg, p.name)
+                elif p.default is p.empty:
+                    raise NotImplementedError(f"{cls.__name__}: no value for constructor argument '{p.name}' in the config")
+            return cls(**init_args)
 
 logger.info("lip2speech_unit_amd plugin mode: %s", "fairseq (classes extend FairseqTask / BaseFairseqModel)"
             if HAVE_FAIRSEQ else "stand-alone (fairseq not importable; local registries only)")
@@ -94,6 +122,24 @@ def register_model(name, dataclass=None):
         MODEL_REGISTRY[name] = (cls, dataclass)
         return cls
     return deco
+
+
+def register_criterion(name, dataclass=None):
+    def deco(cls):
+        if HAVE_FAIRSEQ:
+            cls = _fairseq_register_criterion(name, dataclass=dataclass)(cls)
+        CRITERION_REGISTRY[name] = (cls, dataclass)
+        return cls
+    return deco
+
+
+def log_scalar(key, value, weight=1, round=None):
+    """`fairseq.metrics.log_scalar` when a fairseq trainer has its meters loaded (fairseq.logging.metrics; `fairseq.metrics` up to
+    0.10), nothing otherwise: the stand-alone CLI reports through MultiTargetCriterion.aggregate."""
+    import sys
+    m = sys.modules.get("fairseq.logging.metrics") or sys.modules.get("fairseq.metrics")
+    if HAVE_FAIRSEQ and m is not None:
+        m.log_scalar(key, value, weight, round=round)
 
 
 def cfg_get(cfg, key, default=None):

@@ -170,10 +170,12 @@ class Lip2SpeechTask(TaskBase):
 
     def load_dataset(self, split: str, **kwargs):
         from .data import MultiTargetDataset
+        # text supervision: <label_dir>/<split>.txt, one line of piece ids per clip (already tokenised); absent = no text labels
+        text_path = f"{self.get_label_dir()}/{split}.txt" if cfg_get(self.cfg, "text_supervision", False) else None
         self.datasets[split] = MultiTargetDataset(
             f"{self.cfg.data}/{split}.tsv", label_path=f"{self.get_label_dir()}/{split}.{self.cfg.labels[0]}",
             label_processor=LabelEncoderUnit(self._dict), pad=self._dict.pad(), image_mean=self.cfg.image_mean,
-            image_std=self.cfg.image_std, image_crop_size=self.cfg.image_crop_size)
+            image_std=self.cfg.image_std, image_crop_size=self.cfg.image_crop_size, text_label_path=text_path)
         return self.datasets[split]
 
     def dataset(self, split):
@@ -196,6 +198,30 @@ class Lip2SpeechTask(TaskBase):
             match_source_len=getattr(args, "match_source_len", False),
             no_repeat_ngram_size=getattr(args, "no_repeat_ngram_size", 0), search_strategy=None,
             nbest=getattr(args, "nbest", 1), use_hipgraph=getattr(args, "hipgraph", False), **extra)
+
+    def build_criterion(self, cfg):
+        """FairseqTask.build_criterion: the criterion named by `cfg._name` (criterion: multi_target in the fine-tuning yaml),
+        constructed from the config's fields.  `cfg` may be a dict (what a checkpoint stores), a dataclass or a DictConfig."""
+        from . import criterion as _criterion      # noqa: F401  (registers multi_target)
+        from .plugin import CRITERION_REGISTRY
+        name = cfg_get(cfg, "_name", None) or "multi_target"
+        if name not in CRITERION_REGISTRY:
+            raise KeyError(f"criterion '{name}' is not registered (known: {', '.join(sorted(CRITERION_REGISTRY))})")
+        cls, dc = CRITERION_REGISTRY[name]
+        if isinstance(cfg, dict) and dc is not None:
+            known = set(dc.__dataclass_fields__)
+            unknown = [k for k in cfg if k not in known]
+            if unknown:
+                raise KeyError(f"criterion config: unknown key(s) {unknown} for '{name}'")
+            cfg = dc(**cfg)
+        return cls.build_criterion(cfg, self)
+
+    def valid_step(self, sample, model, criterion):
+        """FairseqTask.valid_step: (loss, sample_size, logging_output) of one batch, no gradients."""
+        model.eval()
+        with torch.no_grad():
+            loss, sample_size, logging_output = criterion(model, sample)
+        return loss, sample_size, logging_output
 
     def inference_step(self, generator, models, sample, prefix_tokens=None, constraints=None):
         with torch.no_grad():
