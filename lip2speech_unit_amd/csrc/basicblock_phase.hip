@@ -36,7 +36,7 @@
 // CH = 64 scheme).  Up to four blocks run back to back: a block's output stays in registers as the next block's residual and goes
 // back into the region as its input - the 16-bit values a launch of its own would read back, so the result is bit-identical to
 // one launch per block.
-#include "tapgemm_common.h"
+#include "phase_stream.h"
 #include <cstdlib>
 
 using namespace l2s;
@@ -87,22 +87,6 @@ __device__ __forceinline__ P bp_pick(const P (&arr)[BP_MAXCV], int i) {
   return r;
 }
 
-__device__ __forceinline__ void bp_write_u4(uint32_t addr, u32x4_t v) {
-  asm volatile("ds_write_b128 %0, %1" ::"v"(addr), "v"(v) : "memory");
-}
-// (reads that stay live across a convolution carry their own wait: see respair_phase.hip)
-__device__ __forceinline__ void bp_read8_u4_sync(u32x4_t (&v)[4][2], const uint32_t (&ad)[4][2]) {
-  asm volatile("ds_read_b128 %0, %8\n\tds_read_b128 %1, %9\n\tds_read_b128 %2, %10\n\tds_read_b128 %3, %11\n\t"
-               "ds_read_b128 %4, %12\n\tds_read_b128 %5, %13\n\tds_read_b128 %6, %14\n\tds_read_b128 %7, %15\n\ts_waitcnt lgkmcnt(0)"
-               : "=&v"(v[0][0]), "=&v"(v[0][1]), "=&v"(v[1][0]), "=&v"(v[1][1]), "=&v"(v[2][0]), "=&v"(v[2][1]), "=&v"(v[3][0]), "=&v"(v[3][1])
-               : "v"(ad[0][0]), "v"(ad[0][1]), "v"(ad[1][0]), "v"(ad[1][1]), "v"(ad[2][0]), "v"(ad[2][1]), "v"(ad[3][0]), "v"(ad[3][1]));
-}
-__device__ __forceinline__ void bp_read4_f4_sync(f32x4_t (&v)[4], const uint32_t (&ad)[4]) {
-  asm volatile("ds_read_b128 %0, %4\n\tds_read_b128 %1, %5\n\tds_read_b128 %2, %6\n\tds_read_b128 %3, %7\n\ts_waitcnt lgkmcnt(0)"
-               : "=&v"(v[0]), "=&v"(v[1]), "=&v"(v[2]), "=&v"(v[3])
-               : "v"(ad[0]), "v"(ad[1]), "v"(ad[2]), "v"(ad[3]));
-}
-
 template <typename ET, int CH_, int H_, int W_, bool TAIL>
 __global__ __launch_bounds__(512) void basicblock_phase_kernel(const BpArgs a) {
   using G = PGeo<CH_, H_, W_, TAIL>;
@@ -122,7 +106,6 @@ __global__ __launch_bounds__(512) void basicblock_phase_kernel(const BpArgs a) {
   const int ncv = 2 * a.nb;                    // convolutions of the blocks (TAIL: conv A comes before them)
 
   const uint32_t lds_base = (uint32_t)(uintptr_t)(lptr_t)lds;
-  const uint32_t wring = lds_base + G::RING_OFF;
 
   // ---- patch: PI instructions of 8 region rows x 128 B; region row R of a block = padded position R % IMGP of image R / IMGP ----
   auto issue_patch = [&](int i) {
@@ -190,27 +173,16 @@ __global__ __launch_bounds__(512) void basicblock_phase_kernel(const BpArgs a) {
     }
   };
 
-  // ---- fragments ----
-  uint32_t wP, wQ;
-  {
-    const int row0 = 8 * (lm >> 2) + (lm & 3);
-    const int c0 = lg ^ paired_w_key(row0);
-    wP = wring + (uint32_t)(wc * 4096 + row0 * 128 + (c0 << 4));
-    wQ = wring + (uint32_t)(wc * 4096 + row0 * 128 + ((c0 ^ 4) << 4));
-  }
-  frag16 fa[MI][2], fb[2][2];
-  auto read_b = [&](auto slot_tag) {
-    constexpr int SO = decltype(slot_tag)::value * G::Q_B;
-    lds_read_b128<SO>(fb[0][0], wP); lds_read_b128<SO + 512>(fb[1][0], wQ);
-    lds_read_b128<SO>(fb[0][1], wQ); lds_read_b128<SO + 512>(fb[1][1], wP);
-  };
+  // ---- fragments and the phase step (phase_stream.h): paired W order, one staging instruction per wave and quarter ----
+  PhaseStream<ET, G::Q_B, 1, true> ps;
+  ps.init(lds_base + G::RING_OFF, wc, lm, lg);
   // per row group: the k-step 0 address of the tap's row in channel block 0; k-step 1 is the same row at chunk ^ 4
   auto read_a = [&](auto off_tag, const uint32_t (&a0)[MI]) {
     constexpr int AO = decltype(off_tag)::value;
 #pragma unroll
-    for (int i = 0; i < MI; ++i) lds_read_b128<AO>(fa[i][0], a0[i]);
+    for (int i = 0; i < MI; ++i) lds_read_b128<AO>(ps.fa[i][0], a0[i]);
 #pragma unroll
-    for (int i = 0; i < MI; ++i) lds_read_b128<AO>(fa[i][1], a0[i] ^ 64u);
+    for (int i = 0; i < MI; ++i) lds_read_b128<AO>(ps.fa[i][1], a0[i] ^ 64u);
   };
 
   // ---- per-lane geometry of the four row groups (the same for every tile) ----
@@ -242,7 +214,7 @@ __global__ __launch_bounds__(512) void basicblock_phase_kernel(const BpArgs a) {
     uint32_t ad[4];
 #pragma unroll
     for (int j = 0; j < NI; ++j) ad[j] = tab_ad[j] + (uint32_t)(which * CH * 4);
-    bp_read4_f4_sync(v, ad);
+    lds_read4_f4_sync(v, ad);
   };
   auto init_acc = [&](const int which) {
     f32x4_t bj[NI];
@@ -259,30 +231,7 @@ __global__ __launch_bounds__(512) void basicblock_phase_kernel(const BpArgs a) {
   uint32_t a0[MI];
   // one phase = one quarter (ring slot SLOT): half H of the wave's 64 columns x all 64 rows x K = 64
   auto phase = [&](auto h_tag, auto slot_tag, auto aoff_tag) {
-    constexpr int H = decltype(h_tag)::value, SLOT = decltype(slot_tag)::value;
-    read_b(slot_tag);
-    if (H == 0) { __builtin_amdgcn_sched_barrier(0); read_a(aoff_tag, a0); }
-    stage_one(std::integral_constant<int, (SLOT + 2) & 3>{}, h_tag);   // quarter g+2 (the same half) -> the slot of quarter g-2
-    __builtin_amdgcn_sched_barrier(0);
-    wait_vmcnt<1>();                           // quarter g+1 (staged one phase ago) has landed: read one barrier from now
-    asm volatile("" ::: "memory");
-    __builtin_amdgcn_s_barrier();
-    asm volatile("" ::: "memory");
-    lds_wait();
-    __builtin_amdgcn_s_setprio(1);
-#pragma unroll
-    for (int i = 0; i < MI; ++i)
-#pragma unroll
-      for (int s2 = 0; s2 < 2; ++s2) {
-        acc[i][2 * H + s2] = ET::mfma(fb[s2][0], fa[i][0], acc[i][2 * H + s2]);
-        acc[i][2 * H + s2] = ET::mfma(fb[s2][1], fa[i][1], acc[i][2 * H + s2]);
-      }
-    __builtin_amdgcn_s_setprio(0);
-    __builtin_amdgcn_sched_barrier(0);         // (nothing between the last MFMA and the barrier, nothing hoisted above it: respair_phase.hip)
-    asm volatile("" ::: "memory");
-    __builtin_amdgcn_s_barrier();
-    asm volatile("" ::: "memory");
-    __builtin_amdgcn_sched_barrier(0);
+    ps.template step<decltype(h_tag)::value, decltype(slot_tag)::value>(acc, [&]() { read_a(aoff_tag, a0); }, stage_one);
   };
   auto tap_addr = [&](int shift) {
 #pragma unroll
@@ -391,8 +340,8 @@ __global__ __launch_bounds__(512) void basicblock_phase_kernel(const BpArgs a) {
       for (int i = 0; i < MI; ++i)
         if (wr * 64 + i * 16 + lm < G::IPT * G::HW) {
           const uint32_t ca = chunk_ad(i);
-          bp_write_u4(ca, o16[i][0]);
-          bp_write_u4(ca ^ 64u, o16[i][1]);
+          lds_write_u4(ca, o16[i][0]);
+          lds_write_u4(ca ^ 64u, o16[i][1]);
         }
       init_acc(next_bias);
       asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
@@ -422,7 +371,7 @@ __global__ __launch_bounds__(512) void basicblock_phase_kernel(const BpArgs a) {
         uint32_t ad[MI][2];
 #pragma unroll
         for (int i = 0; i < MI; ++i) { ad[i][0] = chunk_ad(i); ad[i][1] = ad[i][0] ^ 64u; }
-        bp_read8_u4_sync(resp, ad);
+        lds_read8_u4_sync(resp, ad);
       }
       {
         u32x4_t t1v[MI][2];

@@ -396,7 +396,7 @@ __global__ __launch_bounds__(512) void phasegemm_kernel(const l2s_gemm_desc p, c
     __builtin_amdgcn_s_setprio(0);
     // Nothing may sit between the last MFMA and the barrier: the partner wave of this SIMD starts its MFMAs behind it.  Without the
     // fence AFTER the barrier hipcc hoists the next phase's address arithmetic above it (round 4, read off the ISA: ~20 SALU / VALU
-    // instructions per phase on the MFMA path; csrc/respair256.hip measured 800 -> 610 cycles per phase from this and leaner staging)
+    // instructions per phase on the MFMA path; csrc/respair_phase.hip measured 800 -> 610 cycles per phase from this and leaner staging)
     __builtin_amdgcn_sched_barrier(0);
     asm volatile("" ::: "memory");
     __builtin_amdgcn_s_barrier();

@@ -17,7 +17,7 @@
 // (MI = 3, NI = 4), 4 waves and two blocks per CU at C = 64 (80 KB each), 8 waves and one block at C = 128 (160 KB).  The next
 // tile's patch DMA is issued as soon as conv2 has finished reading t1 and travels under the epilogue, which touches no
 // global memory besides its stores (the mid-pair epilogue: residual from registers, the clip length is tile-uniform).
-#include "tapgemm_common.h"
+#include "phase_stream.h"
 #include "respair_args.h"
 #include <cstdlib>
 
@@ -58,17 +58,9 @@ __global__ __launch_bounds__(CH * 4, (CH == 64 ? 2 : 1)) void respair_kernel(con
   const int k = a.k, dil = a.dil, h1 = a.h1, h2 = a.h2, T = a.T;
   const int Ktot = k * CH;
   const uint16_t* zero = reinterpret_cast<const uint16_t*>(&g_zero16);
-  // tiles of this block: its XCD's range [xcd*per, min((xcd+1)*per, ntiles)) walked with stride gridDim/8 from offset bx
-  int my_n = 0;
-  if (!a.xcd_order) {
-    my_n = (a.ntiles - (int)blockIdx.x + (int)gridDim.x - 1) / (int)gridDim.x;
-  } else {
-    const int per = (a.ntiles + 7) >> 3, lo = ((int)blockIdx.x & 7) * per;
-    int hi = lo + per;
-    hi = hi < a.ntiles ? hi : a.ntiles;
-    const int gxx = ((int)gridDim.x + 7) >> 3, b8 = (int)blockIdx.x >> 3;
-    if (lo + b8 < hi) my_n = (hi - lo - b8 + gxx - 1) / gxx;
-  }
+  // tiles of this block, in XCD-aware order by default (phase_stream.h: neighbouring tiles share their 2*(h1+h2) halo rows in one L2)
+  const TileWalk tiles(a.ntiles, a.xcd_order);
+  const int my_n = tiles.n;
   if (my_n <= 0) return;
   const int nel = k * HALVES;               // stream elements per convolution: (tap, K half)
   const int total = my_n * 2 * nel;         // weight stream across both convolutions of all of this block's tiles
@@ -77,17 +69,8 @@ __global__ __launch_bounds__(CH * 4, (CH == 64 ? 2 : 1)) void respair_kernel(con
   const uint32_t wring = lds_base + REGION_A;
   const uint32_t scr = wring + RQ * QEL_B + (uint32_t)wave * 4096;
 
-  // XCD-aware tile order: blocks b and b+8 share an XCD (and its L2), so each XCD walks ONE contiguous range of the tile
-  // list and the blocks of an XCD work on neighbouring tiles at the same time - the 2*(h1+h2) halo rows two neighbours
-  // share are then fetched from HBM once instead of once per XCD (speed only: any order is correct)
-  const int xcd = blockIdx.x & 7, bx = blockIdx.x >> 3, gx = (gridDim.x + 7) >> 3;
-  const int per_xcd = (a.ntiles + 7) >> 3;
-  auto tile_index = [&](int i) { return a.xcd_order ? xcd * per_xcd + bx + i * gx : (int)blockIdx.x + i * (int)gridDim.x; };
-  auto tile_origin = [&](int i, int& unit, int& g0) {
-    const int L = tile_index(i);
-    unit = L / a.tiles_per_clip;
-    g0 = (L - unit * a.tiles_per_clip) * a.S - h2;      // global time of conv row 0 (t1 row 0 / output row 0)
-  };
+  // (unit, g0): the clip and the global time of conv row 0 (t1 row 0 / output row 0)
+  auto tile_origin = [&](int i, int& unit, int& g0) { tiles.origin(i, a.tiles_per_clip, a.S, h2, unit, g0); };
   auto issue_patch = [&](int i) {
     int unit, g0;
     tile_origin(i, unit, g0);
@@ -344,7 +327,7 @@ int launch_respair(const RpArgs& a, hipStream_t st) {
 
 }  // namespace
 
-// respair_phase.hip: the C = 256 and C = 128 stages on the phase-staggered schedule
+// respair_phase.hip: the C = 256, C = 128 and C = 64 stages on the phase-staggered schedule
 int l2s_respair_phase_rows(int C);
 bool l2s_respair_phase_supports(int C, int h1, int h2);
 int l2s_respair_phase_launch(const RpArgs& a, int C, int dtype, int kind, hipStream_t st);

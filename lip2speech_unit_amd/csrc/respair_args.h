@@ -1,4 +1,4 @@
-// Arguments shared by the fused conv-pair kernels (respair.hip: C = 64 / 128; respair256.hip: C = 256).
+// Arguments shared by the fused conv-pair kernels (respair.hip: C = 64 / 128; respair_phase.hip: C = 256 / 128 / 64).
 #pragma once
 #include <stdint.h>
 

@@ -24,7 +24,7 @@
 //     channels: t1 rows are written back by ds_write_b128 and leaky_relu(x') leaves through epilogue_direct16 as whole 128-byte
 //     lines, no LDS scratch (there is none left: 92 + 64 KB); last pairs keep the plain order, in which a lane owns 4
 //     consecutive fp32 channels of the ResBlock sum (16-byte accesses).
-#include "tapgemm_common.h"
+#include "phase_stream.h"
 #include "respair_args.h"
 #include <cstdlib>
 
@@ -58,33 +58,6 @@ struct XGeo {
   static_assert(RPR % 8 == 0 && (CH == 256 || (NBLK - 1) * BLK_B + 6144 < 65536), "geometry");
 };
 
-__device__ __forceinline__ void lds_write_u4(uint32_t addr, u32x4_t v) {
-  asm volatile("ds_write_b128 %0, %1" ::"v"(addr), "v"(v) : "memory");
-}
-// Reads whose results must survive a long stretch of code (the residual rows: held across the whole second convolution) carry
-// their own wait: after an asm LDS read without one the compiler believes the destination is valid at once, and under
-// register pressure it may spill the register BEFORE the separate s_waitcnt - the spill slot then holds the stale contents
-// (seen with the last-pair epilogue: garbage in exactly the spilled (row group, block) entries).
-__device__ __forceinline__ void lds_read4_u2_sync(u32x2_t (&v)[4], const uint32_t (&ad)[4]) {
-  asm volatile("ds_read_b64 %0, %4\n\tds_read_b64 %1, %5\n\tds_read_b64 %2, %6\n\tds_read_b64 %3, %7\n\ts_waitcnt lgkmcnt(0)"
-               : "=&v"(v[0]), "=&v"(v[1]), "=&v"(v[2]), "=&v"(v[3])
-               : "v"(ad[0]), "v"(ad[1]), "v"(ad[2]), "v"(ad[3]));
-}
-__device__ __forceinline__ void lds_read8_u4_sync(u32x4_t (&v)[4][2], const uint32_t (&ad)[4][2]) {
-  asm volatile("ds_read_b128 %0, %8\n\tds_read_b128 %1, %9\n\tds_read_b128 %2, %10\n\tds_read_b128 %3, %11\n\t"
-               "ds_read_b128 %4, %12\n\tds_read_b128 %5, %13\n\tds_read_b128 %6, %14\n\tds_read_b128 %7, %15\n\ts_waitcnt lgkmcnt(0)"
-               : "=&v"(v[0][0]), "=&v"(v[0][1]), "=&v"(v[1][0]), "=&v"(v[1][1]), "=&v"(v[2][0]), "=&v"(v[2][1]), "=&v"(v[3][0]), "=&v"(v[3][1])
-               : "v"(ad[0][0]), "v"(ad[0][1]), "v"(ad[1][0]), "v"(ad[1][1]), "v"(ad[2][0]), "v"(ad[2][1]), "v"(ad[3][0]), "v"(ad[3][1]));
-}
-__device__ __forceinline__ void lds_read4_f4_sync(f32x4_t (&v)[4], const uint32_t (&ad)[4]) {
-  asm volatile("ds_read_b128 %0, %4\n\tds_read_b128 %1, %5\n\tds_read_b128 %2, %6\n\tds_read_b128 %3, %7\n\ts_waitcnt lgkmcnt(0)"
-               : "=&v"(v[0]), "=&v"(v[1]), "=&v"(v[2]), "=&v"(v[3])
-               : "v"(ad[0]), "v"(ad[1]), "v"(ad[2]), "v"(ad[3]));
-}
-__device__ __forceinline__ void lds_write_u2(uint32_t addr, u32x2_t v) {
-  asm volatile("ds_write_b64 %0, %1" ::"v"(addr), "v"(v) : "memory");
-}
-
 // Diagnostic build (-DL2S_PAIR_STAMPS, tools/pair_stamps.py): waves 0 and 7 of every block accumulate s_memtime deltas of
 // [0] the wait at the tile start (patch + first quarters), [1] conv1, [2] the patch -> t1 hand-over (after [7], the wait that levels
 // the wave rows), [3] conv2, [5] the levelling wait behind conv2, [6] the next patch's DMA issue, [4] the epilogue proper.
@@ -95,87 +68,53 @@ __device__ unsigned long long* g_pair_stamps = nullptr;
 #define PRSTAMP(i)
 #endif
 
-// KIND 0: mid pair (Y = leaky_relu(x'));  KIND 1: last pair of a ResBlock (XS (+)= x', optional Y = leaky_relu(XS))
-template <typename ET, int CH, int KIND>
-__global__ __launch_bounds__(512) void respair_phase_kernel(const RpArgs a) {
+// What both pair kernels are built from: the block's geometry, the patch DMA, the staging DMA of a weight quarter, one convolution
+// out of the region on the phase step of phase_stream.h, the residual rows and the conv1 -> t1 hand-over.  PAIRED: the weight
+// fragments' row order (the header comment's last point).  The weight CURSOR (which quarter comes next) belongs to the kernel: it
+// hands it to run_conv as stage_one(slot tag, half tag).
+template <typename ET, int CH, bool PAIRED>
+struct PairCore {
   using G = XGeo<CH>;
-  constexpr int MI = 4, NI = 4;
-  constexpr bool PAIRED = KIND == 0;
-  extern __shared__ __attribute__((aligned(16))) uint16_t lds[];
-  const int tid = threadIdx.x, lane = tid & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int wr = wave / G::NWC, wc = wave % G::NWC;
-  const bool upper = wave >= 4;                // the second wave of every SIMD: runs one barrier behind
-  const int lm = lane & 15, lg = lane >> 4;
-  const int srow = lane >> 3, schunk = (lane & 7) ^ (srow & 7);
-  const int k = a.k, dil = a.dil, h1 = a.h1, h2 = a.h2, T = a.T;
-  const int Ktot = k * CH;
-  const uint16_t* zero = reinterpret_cast<const uint16_t*>(&g_zero16);
+  static constexpr int MI = 4, NI = 4;
+  using Acc = f32x4_t[MI][NI];
+  uint16_t* lds;
+  int lane, wave, wr, wc, lm, lg, srow, schunk;
+  bool upper;                                  // the second wave of every SIMD: runs one barrier behind
+  uint32_t lds_base;
+  PhaseStream<ET, G::Q_B, G::DPW, PAIRED> ps;
+  // weight staging: quarter (conv, K-tile, half h) = rows {wc*64 + 32 h + 0..31}; wave w stages quarter rows w * QROWS/8 .. +
+  // QROWS/8 - 1 (16 or 8: two or one instruction of 8 rows).  Source = the kernel's uniform cursor (SGPR pair) + one per-lane
+  // 32-bit byte offset per instruction, row * (k * CH * 2) + chunk: no 64-bit vector arithmetic in the loop
+  bool stager;
+  int sw;                                      // index among the staging waves
+  uint32_t w_row[G::DPW], w_chunk[G::DPW];
+  uint32_t bias_ad[NI];                        // this lane's channels in the fp32 vectors stashed at BIAS_OFF
 
-  // ---- tiles of this block (respair.hip's XCD-aware order: blocks b and b+8 share an L2 and walk neighbouring tiles) ----
-  int my_n = 0;
-  if (!a.xcd_order) {
-    my_n = (a.ntiles - (int)blockIdx.x + (int)gridDim.x - 1) / (int)gridDim.x;
-  } else {
-    const int per = (a.ntiles + 7) >> 3, lo = ((int)blockIdx.x & 7) * per;
-    int hi = lo + per;
-    hi = hi < a.ntiles ? hi : a.ntiles;
-    const int gxx = ((int)gridDim.x + 7) >> 3, b8 = (int)blockIdx.x >> 3;
-    if (lo + b8 < hi) my_n = (hi - lo - b8 + gxx - 1) / gxx;
-  }
-  if (my_n <= 0) return;
-  const int nkt = k * G::NBLK;               // K-tiles per convolution: (tap, 64-channel block)
-  const int xcd = blockIdx.x & 7, bx = blockIdx.x >> 3, gx = (gridDim.x + 7) >> 3;
-  const int per_xcd = (a.ntiles + 7) >> 3;
-  auto tile_origin = [&](int i, int& unit, int& g0) {
-    const int L = a.xcd_order ? xcd * per_xcd + bx + i * gx : (int)blockIdx.x + i * (int)gridDim.x;
-    unit = L / a.tiles_per_clip;
-    g0 = (L - unit * a.tiles_per_clip) * a.S - h2;      // global time of conv row 0 (t1 row 0 / output row 0)
-  };
-
-  const uint32_t lds_base = (uint32_t)(uintptr_t)(lptr_t)lds;
-  const uint32_t wring = lds_base + G::REGION;
-
-  // ---- patch: PI instructions of 8 rows x 128 B, PPW per wave (the last wave has fewer); rows past the patch are not fetched ----
-  const int patch_rows = G::RM + 2 * h1;
-  auto issue_patch = [&](int i) {
-    int unit, g0;
-    tile_origin(i, unit, g0);
+  __device__ __forceinline__ PairCore(uint16_t* lds_, int tid)
+      : lds(lds_), lane(tid & 63), wave(__builtin_amdgcn_readfirstlane(tid >> 6)), wr(wave / G::NWC), wc(wave % G::NWC),
+        lm(lane & 15), lg(lane >> 4), srow(lane >> 3), schunk((lane & 7) ^ (srow & 7)), upper(wave >= 4),
+        lds_base((uint32_t)(uintptr_t)(lptr_t)lds_),
+        stager(CH >= 128 || !(wave & 1)), sw(CH >= 128 ? wave : wave >> 1) {
 #pragma unroll
-    for (int j = 0; j < G::PPW; ++j) {
-      const int instr = wave * G::PPW + j;
-      const int cq = instr / (G::RPR / 8), blk = instr - cq * (G::RPR / 8);
-      if (instr < G::PI && blk * 8 < patch_rows) {
-        const int ts = g0 - h1 + blk * 8 + srow;
-        const uint16_t* g = ((unsigned)ts < (unsigned)T) ? a.X + ((int64_t)unit * T + ts) * CH + cq * 64 + schunk * 8 : zero;
-        __builtin_amdgcn_global_load_lds((gptr_t)g, (lptr_t)(lds + cq * (G::BLK_B / 2) + blk * 512), 16, 0, 0);
-      }
+    for (int j = 0; j < G::DPW; ++j) {
+      const int qrow = sw * G::RPS + 8 * j + srow;                 // row of the quarter: wave column qrow / 32, row qrow % 32 of its share
+      const int within = qrow & 31;
+      w_row[j] = (uint32_t)((qrow >> 5) * 64 + within);
+      w_chunk[j] = (uint32_t)((PAIRED ? ((lane & 7) ^ paired_w_key(within)) : schunk) * 16);
     }
-  };
-
-  // ---- weight stream: quarter (conv, K-tile, half h) = rows {wc*64 + 32 h + 0..31}; wave w stages quarter rows
-  // w * QROWS/8 .. + QROWS/8 - 1 (16 or 8: two or one instruction of 8 rows) ----
-  // source = uniform cursor (SGPR pair) + one per-lane 32-bit byte offset per instruction: no 64-bit vector arithmetic in the loop
-  const bool stager = CH >= 128 || !(wave & 1);
-  const int sw = CH >= 128 ? wave : wave >> 1;                   // index among the staging waves
-  uint32_t w_lane[G::DPW];
+    ps.init(lds_base + G::REGION, wc, lm, lg);
+    // channel of acc[i][j][e]: paired: wc*64 + 32 (j >> 1) + 8 lg + 4 (j & 1) + e;  plain: wc*64 + 16 j + 4 lg + e
 #pragma unroll
-  for (int j = 0; j < G::DPW; ++j) {
-    const int qrow = sw * G::RPS + 8 * j + srow;                 // row of the quarter: wave column qrow / 32, row qrow % 32 of its share
-    const int within = qrow & 31;
-    const int n = (qrow >> 5) * 64 + within;
-    const int chunk = PAIRED ? ((lane & 7) ^ paired_w_key(within)) : schunk;
-    w_lane[j] = (uint32_t)(n * Ktot + chunk * 8) * 2u;
+    for (int j = 0; j < NI; ++j)
+      bias_ad[j] = lds_base + G::BIAS_OFF + (uint32_t)((PAIRED ? wc * 64 + 32 * (j >> 1) + 8 * lg + 4 * (j & 1) : wc * 64 + 16 * j + 4 * lg) * 4);
   }
-  const uint32_t h_bytes = (uint32_t)(32 * Ktot) * 2u;
-  // cursor: the K-tile being staged (uniform pointer to its first half) - it simply keeps cycling W1 -> W2 -> W1 ..., so the
-  // stagings past the block's last quarter re-fetch the first quarters of W1 into slots nobody reads (valid memory, exact counts)
-  const char* kt_ptr = (const char*)a.W1;
-  int s_kt = 0, s_conv = 0;
-  // exactly DPW LDS-DMA instructions per wave into slot DSLOT (a compile-time LDS address: M0 is one s_mov) for half SH of the K-tile
-  auto stage_one = [&](auto dslot_tag, auto sh_tag) {
-    constexpr int DSLOT = decltype(dslot_tag)::value, SH = decltype(sh_tag)::value;
-    const char* wb = kt_ptr + (size_t)(SH ? h_bytes : 0u);
+  __device__ __forceinline__ void lane_offsets(uint32_t (&w_lane)[G::DPW], int k) const {
+#pragma unroll
+    for (int j = 0; j < G::DPW; ++j) w_lane[j] = w_row[j] * (uint32_t)(k * CH * 2) + w_chunk[j];
+  }
+  // exactly DPW LDS-DMA instructions per wave into slot DSLOT (a compile-time LDS address: M0 is one s_mov)
+  template <int DSLOT>
+  __device__ __forceinline__ void stage_quarter(const char* wb, const uint32_t (&w_lane)[G::DPW]) const {
     uint16_t* dst = lds + G::REGION / 2 + DSLOT * (G::Q_B / 2) + sw * G::RPS * 64;
 #pragma unroll
     for (int j = 0; j < G::DPW; ++j) {
@@ -185,48 +124,26 @@ __global__ __launch_bounds__(512) void respair_phase_kernel(const RpArgs a) {
       asm volatile("" ::"v"(wb + (size_t)w_lane[j]), "v"(dst));
 #endif
     }
-    if constexpr (SH == 1) {
-      kt_ptr += 128;
-      if (++s_kt == nkt) { s_kt = 0; s_conv ^= 1; kt_ptr = (const char*)(s_conv ? a.W2 : a.W1); }
-    }
-  };
-
-  // ---- fragments: two per-lane bases each for W and A, everything else is an immediate offset ----
-  // W quarter, this wave column's 32 rows (4 KB).  plain order: block s, k-step ks at  s*2048 + lm*128 + ((4ks + lg) ^ (lm & 7))*16;
-  // paired order (paired_w_off): row 8 (lm >> 2) + 4 s + (lm & 3), chunk (lg ^ key0) ^ 4 (ks ^ s): with c0 = lg ^ key0 the four
-  // fragments sit at P, Q (ks = 1), Q + 512 (s = 1), P + 512 (s = 1, ks = 1) for P = row0 + c0*16, Q = row0 + (c0 ^ 4)*16
-  uint32_t wP, wQ;
-  if constexpr (PAIRED) {
-    const int row0 = 8 * (lm >> 2) + (lm & 3);
-    const int c0 = lg ^ paired_w_key(row0);
-    wP = wring + (uint32_t)(wc * 4096 + row0 * 128 + (c0 << 4));
-    wQ = wring + (uint32_t)(wc * 4096 + row0 * 128 + ((c0 ^ 4) << 4));
-  } else {
-    wP = wring + (uint32_t)(wc * 4096 + lm * 128 + (((0 + lg) ^ (lm & 7)) << 4));
-    wQ = wring + (uint32_t)(wc * 4096 + lm * 128 + (((4 + lg) ^ (lm & 7)) << 4));
   }
-  frag16 fa[MI][2], fb[2][2];
-  auto read_b = [&](auto slot_tag) {
-    constexpr int SO = decltype(slot_tag)::value * G::Q_B;
-    if constexpr (PAIRED) {
-      lds_read_b128<SO>(fb[0][0], wP); lds_read_b128<SO + 512>(fb[1][0], wQ);
-      lds_read_b128<SO>(fb[0][1], wQ); lds_read_b128<SO + 512>(fb[1][1], wP);
-    } else {
-      lds_read_b128<SO>(fb[0][0], wP); lds_read_b128<SO + 2048>(fb[1][0], wP);
-      lds_read_b128<SO>(fb[0][1], wQ); lds_read_b128<SO + 2048>(fb[1][1], wQ);
+  // patch of the tile at (unit, g0): PI instructions of 8 rows x 128 B, PPW per wave (the last wave has fewer); rows past the
+  // patch (RM + 2 h1) are not fetched
+  __device__ __forceinline__ void issue_patch(const uint16_t* X, int unit, int g0, int h1, int T) const {
+    const uint16_t* zero = reinterpret_cast<const uint16_t*>(&g_zero16);
+    const int patch_rows = G::RM + 2 * h1;
+#pragma unroll
+    for (int j = 0; j < G::PPW; ++j) {
+      const int instr = wave * G::PPW + j;
+      const int cq = instr / (G::RPR / 8), blk = instr - cq * (G::RPR / 8);
+      if (instr < G::PI && blk * 8 < patch_rows) {
+        const int ts = g0 - h1 + blk * 8 + srow;
+        const uint16_t* g = ((unsigned)ts < (unsigned)T) ? X + ((int64_t)unit * T + ts) * CH + cq * 64 + schunk * 8 : zero;
+        __builtin_amdgcn_global_load_lds((gptr_t)g, (lptr_t)(lds + cq * (G::BLK_B / 2) + blk * 512), 16, 0, 0);
+      }
     }
-  };
-  auto read_a = [&](auto off_tag, uint32_t a0, uint32_t a1) {
-    constexpr int AO = decltype(off_tag)::value;
-    lds_read_b128<AO>(fa[0][0], a0); lds_read_b128<AO + 2048>(fa[1][0], a0); lds_read_b128<AO + 4096>(fa[2][0], a0); lds_read_b128<AO + 6144>(fa[3][0], a0);
-    lds_read_b128<AO>(fa[0][1], a1); lds_read_b128<AO + 2048>(fa[1][1], a1); lds_read_b128<AO + 4096>(fa[2][1], a1); lds_read_b128<AO + 6144>(fa[3][1], a1);
-  };
-
-  f32x4_t acc[MI][NI];
-  // the accumulators start from the convolution's bias (b1 before conv1, b2 before conv2): no bias pass in either epilogue.
-  // The two bias vectors wait in LDS behind the ring (2 KB) instead of 32 registers held across both tap loops.
-  uint32_t bias_ad[NI];
-  auto init_acc = [&](const int which) {
+  }
+  // the accumulators start from a bias vector of the stash (b1 before conv1, b2 before conv2): no bias pass in either epilogue,
+  // and the vectors wait in LDS behind the ring instead of in registers held across both tap loops
+  __device__ __forceinline__ void init_acc(Acc& acc, const int which) const {
     uint32_t ad[4];
 #pragma unroll
     for (int j = 0; j < NI; ++j) ad[j] = bias_ad[j] + (uint32_t)(which * CH * 4);
@@ -236,49 +153,32 @@ __global__ __launch_bounds__(512) void respair_phase_kernel(const RpArgs a) {
     for (int i = 0; i < MI; ++i)
 #pragma unroll
       for (int j = 0; j < NI; ++j) acc[i][j] = bj[j];
-  };
+  }
+  // the wave rows: level (the lower one waits for the upper one's last phase) / a block barrier, then staggered again
+  __device__ __forceinline__ void level() const {
+    if (!upper) __builtin_amdgcn_s_barrier();
+    asm volatile("" ::: "memory");
+  }
+  __device__ __forceinline__ void barrier_then_stagger() const {
+    __builtin_amdgcn_s_barrier();
+    asm volatile("" ::: "memory");
+    if (upper) __builtin_amdgcn_s_barrier();               // the upper wave rows run one barrier behind from here on
+  }
 
-  // one phase = one quarter (ring slot SLOT, a compile-time constant: a tap is 8 phases = two turns of the ring, and every
-  // convolution starts on slot 0): half H of the wave's 64 columns x all 64 rows x K = 64
-  auto phase = [&](auto h_tag, auto slot_tag, auto aoff_tag, uint32_t a0, uint32_t a1) {
-    constexpr int H = decltype(h_tag)::value, SLOT = decltype(slot_tag)::value;
-#ifndef L2S_PAIR_ABL_NOREAD    // (diagnostic, timing only) no fragment reads
-    read_b(slot_tag);
-    if (H == 0) { __builtin_amdgcn_sched_barrier(0); read_a(aoff_tag, a0, a1); }
-#endif
-    stage_one(std::integral_constant<int, (SLOT + 2) & (XRQ - 1)>{}, h_tag);   // quarter g+2 (the same half) -> the slot of quarter g-2
-    __builtin_amdgcn_sched_barrier(0);         // (the staging cursor's bookkeeping stays in front of the wait, off the MFMA path)
-    wait_vmcnt<G::DPW>();                      // quarter g+1 (staged one phase ago) has landed: read one barrier from now
-    asm volatile("" ::: "memory");
-    __builtin_amdgcn_s_barrier();
-    asm volatile("" ::: "memory");
-    lds_wait();
-    __builtin_amdgcn_s_setprio(1);
-#ifndef L2S_PAIR_ABL_NOMFMA    // (diagnostic, timing only) no matrix instructions
-#pragma unroll
-    for (int i = 0; i < MI; ++i)
-#pragma unroll
-      for (int s2 = 0; s2 < 2; ++s2) {
-        acc[i][2 * H + s2] = ET::mfma(fb[s2][0], fa[i][0], acc[i][2 * H + s2]);
-        acc[i][2 * H + s2] = ET::mfma(fb[s2][1], fa[i][1], acc[i][2 * H + s2]);
-      }
-#endif
-    __builtin_amdgcn_s_setprio(0);
-    // nothing may sit between the last MFMA and the barrier: the partner wave of this SIMD starts its MFMAs behind it.  Without the
-    // second fence hipcc hoists the next phase's address arithmetic (16 SALU / VALU instructions, ~80 cycles) above the barrier
-    __builtin_amdgcn_sched_barrier(0);
-    asm volatile("" ::: "memory");
-    __builtin_amdgcn_s_barrier();
-    asm volatile("" ::: "memory");
-    __builtin_amdgcn_sched_barrier(0);
-  };
+  // one K-tile (ring slots SLOT, SLOT + 1) of the A rows at a0 (k-step 0) / a1 (k-step 1), byte offset AO
+  template <int SLOT, int AO, typename ST>
+  __device__ __forceinline__ void ktile(Acc& acc, uint32_t a0, uint32_t a1, ST& stage_one) {
+    auto read_a = [&]() {
+      lds_read_b128<AO>(ps.fa[0][0], a0); lds_read_b128<AO + 2048>(ps.fa[1][0], a0); lds_read_b128<AO + 4096>(ps.fa[2][0], a0); lds_read_b128<AO + 6144>(ps.fa[3][0], a0);
+      lds_read_b128<AO>(ps.fa[0][1], a1); lds_read_b128<AO + 2048>(ps.fa[1][1], a1); lds_read_b128<AO + 4096>(ps.fa[2][1], a1); lds_read_b128<AO + 6144>(ps.fa[3][1], a1);
+    };
+    ps.template step<0, SLOT>(acc, read_a, stage_one);
+    ps.template step<1, SLOT + 1>(acc, read_a, stage_one);
+  }
   // one convolution out of the region: conv 0 reads the patch (row shift tap*dil), conv 1 reads t1 (shift tap - h2 + 8).
   // Per tap two per-lane row addresses (k-steps 0 / 1) for channel blocks 0-1 and two for blocks 2-3 (the 16-bit offset field)
-  using I0 = std::integral_constant<int, 0>; using I1 = std::integral_constant<int, 1>;
-  using I2 = std::integral_constant<int, 2>; using I3 = std::integral_constant<int, 3>;
-  using IB = std::integral_constant<int, G::BLK_B>;
-  auto run_conv = [&](auto conv_tag) {
-    constexpr int conv = decltype(conv_tag)::value;
+  template <int conv, typename ST>
+  __device__ __forceinline__ void run_conv(Acc& acc, int k, int dil, int h2, ST& stage_one) {
     auto row_addr = [&](int tap, uint32_t& a0, uint32_t& a1) {
       const int pr = wr * 64 + lm + (conv == 0 ? tap * dil : tap - h2 + XT1);
       const int x = pr & 7;
@@ -289,94 +189,86 @@ __global__ __launch_bounds__(512) void respair_phase_kernel(const RpArgs a) {
     if constexpr (CH == 64) {
       // one channel block: a tap is two phases; taps in pairs (one turn of the ring), the odd last tap alone.  conv1 starts on
       // slot 0 and leaves the ring half a turn on (k is odd), conv2 starts on slot 2 and brings it back to 0
-      using SA = std::integral_constant<int, conv ? 2 : 0>; using SB = std::integral_constant<int, conv ? 3 : 1>;
-      using SC = std::integral_constant<int, conv ? 0 : 2>; using SD = std::integral_constant<int, conv ? 1 : 3>;
+      constexpr int SA = conv ? 2 : 0;
       int tap = 0;
       for (; tap + 1 < k; tap += 2) {
         uint32_t a0, a1, c0, c1;
         row_addr(tap, a0, a1);
         row_addr(tap + 1, c0, c1);
-        phase(I0{}, SA{}, I0{}, a0, a1); phase(I1{}, SB{}, I0{}, 0u, 0u);
-        phase(I0{}, SC{}, I0{}, c0, c1); phase(I1{}, SD{}, I0{}, 0u, 0u);
+        ktile<SA, 0>(acc, a0, a1, stage_one);
+        ktile<SA ^ 2, 0>(acc, c0, c1, stage_one);
       }
       uint32_t a0, a1;
       row_addr(tap, a0, a1);
-      phase(I0{}, SA{}, I0{}, a0, a1); phase(I1{}, SB{}, I0{}, 0u, 0u);
+      ktile<SA, 0>(acc, a0, a1, stage_one);
     } else {
       for (int tap = 0; tap < k; ++tap) {
         uint32_t a0, a1;
         row_addr(tap, a0, a1);
-        phase(I0{}, I0{}, I0{}, a0, a1); phase(I1{}, I1{}, I0{}, 0u, 0u);      // channel block 0
-        phase(I0{}, I2{}, IB{}, a0, a1); phase(I1{}, I3{}, I0{}, 0u, 0u);      // 1
+        ktile<0, 0>(acc, a0, a1, stage_one);                                    // channel block 0
+        ktile<2, G::BLK_B>(acc, a0, a1, stage_one);                             // 1
         if constexpr (CH == 256) {                                              // (a tap is two turns of the ring; at 128: one)
           const uint32_t c0 = a0 + 2 * G::BLK_B, c1 = a1 + 2 * G::BLK_B;
-          phase(I0{}, I0{}, I0{}, c0, c1); phase(I1{}, I1{}, I0{}, 0u, 0u);    // 2
-          phase(I0{}, I2{}, IB{}, c0, c1); phase(I1{}, I3{}, I0{}, 0u, 0u);    // 3
+          ktile<0, 0>(acc, c0, c1, stage_one);                                  // 2
+          ktile<2, G::BLK_B>(acc, c0, c1, stage_one);                           // 3
         }
       }
     }
-  };
+  }
 
-  // channel of acc[i][j][e]: paired: wc*64 + 32 (j >> 1) + 8 lg + 4 (j & 1) + e;  plain: wc*64 + 16 j + 4 lg + e
-  auto chan = [&](int j) { return PAIRED ? wc * 64 + 32 * (j >> 1) + 8 * lg + 4 * (j & 1) : wc * 64 + 16 * j + 4 * lg; };
+  // the residual rows: the pair's input (LeakyReLU'd) at the conv rows' own time steps, patch row p + h1.
+  // paired: 8 consecutive channels (one 16-byte chunk) per (row group, column half), one LDS round trip for the whole wave tile;
+  // plain: 4 consecutive channels per (row group, block)
+  __device__ __forceinline__ void read_res(u32x4_t (&resp)[MI][2], int h1) const {
+    uint32_t ad[MI][2];
 #pragma unroll
-  for (int j = 0; j < NI; ++j) bias_ad[j] = lds_base + G::BIAS_OFF + (uint32_t)(chan(j) * 4);
-  if (tid < 2 * CH) reinterpret_cast<float*>(lds)[G::BIAS_OFF / 4 + tid] = tid < CH ? a.b1[tid] : a.b2[tid - CH];
-  __syncthreads();
-  const float slope = a.slope, inv_slope = 1.0f / a.slope;
-  init_acc(0);
-
-  issue_patch(0);
-  stage_one(std::integral_constant<int, 0>{}, std::integral_constant<int, 0>{});
-  stage_one(std::integral_constant<int, 1>{}, std::integral_constant<int, 1>{});
-#ifdef L2S_PAIR_STAMPS
-  unsigned long long pr_acc[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-  unsigned long long pr_last = __builtin_amdgcn_s_memtime();
-  const unsigned long long pr_t0 = pr_last;
-#endif
-  for (int c_i = 0; c_i < my_n; ++c_i) {
-    int unit, g0;
-    tile_origin(c_i, unit, g0);
-    int len = a.lens ? a.lens[unit] * a.len_mul : T;
-    len = len < T ? len : T;
-    // ---- tile start (the wave rows are level here): the patch and the first two quarters are visible to every wave ----
-    wait_vmcnt<0>();
-    __builtin_amdgcn_s_barrier();
-    asm volatile("" ::: "memory");
-    if (upper) __builtin_amdgcn_s_barrier();               // the upper wave rows run one barrier behind from here on
-    PRSTAMP(0)
-    run_conv(I0{});
-    PRSTAMP(1)
-
-    // ---- conv1 done.  Level the rows (the lower one waits for the upper one's last phase), save the residual rows, then
-    // t1 = mask(leaky_relu(conv1 + b1)) into the region ----
-    if (!upper) __builtin_amdgcn_s_barrier();
-    asm volatile("" ::: "memory");
-    PRSTAMP(7)
-    u32x4_t resp[MI][2];       // paired: 8 consecutive channels (one 16-byte chunk) per (row group, column half)
-    u32x2_t resq[MI][NI];      // plain: 4 consecutive channels per (row group, block)
-    (void)resp; (void)resq;
-    if constexpr (PAIRED) {
-      uint32_t ad[MI][2];
-#pragma unroll
-      for (int i = 0; i < MI; ++i) {
-        const int R = wr * 64 + i * 16 + lm + h1;          // patch row of conv row p: the pair's input at the same time step
-        const uint32_t ra = lds_base + (uint32_t)wc * G::BLK_B + (uint32_t)R * 128;
-        ad[i][0] = ra + (uint32_t)(((0 + lg) ^ (R & 7)) << 4);
-        ad[i][1] = ra + (uint32_t)(((4 + lg) ^ (R & 7)) << 4);
-      }
-      lds_read8_u4_sync(resp, ad);                         // one LDS round trip for the whole wave tile
-    } else {
-#pragma unroll
-      for (int i = 0; i < MI; ++i) {
-        const int R = wr * 64 + i * 16 + lm + h1;
-        const uint32_t ra = lds_base + (uint32_t)wc * G::BLK_B + (uint32_t)R * 128;
-        uint32_t ad[4];
-#pragma unroll
-        for (int j = 0; j < NI; ++j) ad[j] = ra + (uint32_t)(((2 * j + (lg >> 1)) ^ (R & 7)) << 4) + (uint32_t)((lg & 1) * 8);
-        lds_read4_u2_sync(resq[i], ad);
-      }
+    for (int i = 0; i < MI; ++i) {
+      const int R = wr * 64 + i * 16 + lm + h1;
+      const uint32_t ra = lds_base + (uint32_t)wc * G::BLK_B + (uint32_t)R * 128;
+      ad[i][0] = ra + (uint32_t)(((0 + lg) ^ (R & 7)) << 4);
+      ad[i][1] = ra + (uint32_t)(((4 + lg) ^ (R & 7)) << 4);
     }
+    lds_read8_u4_sync(resp, ad);
+  }
+  __device__ __forceinline__ void read_res(u32x2_t (&resq)[MI][NI], int h1) const {
+#pragma unroll
+    for (int i = 0; i < MI; ++i) {
+      const int R = wr * 64 + i * 16 + lm + h1;
+      const uint32_t ra = lds_base + (uint32_t)wc * G::BLK_B + (uint32_t)R * 128;
+      uint32_t ad[4];
+#pragma unroll
+      for (int j = 0; j < NI; ++j) ad[j] = ra + (uint32_t)(((2 * j + (lg >> 1)) ^ (R & 7)) << 4) + (uint32_t)((lg & 1) * 8);
+      lds_read4_u2_sync(resq[i], ad);
+    }
+  }
+  // acc += x, x recovered from its LeakyReLU'd copy by the inverse of leaky_relu (slope in (0, 1])
+  __device__ __forceinline__ void add_res(Acc& acc, const u32x4_t (&resp)[MI][2], float inv_slope) const {
+#pragma unroll
+    for (int i = 0; i < MI; ++i)
+#pragma unroll
+      for (int h = 0; h < 2; ++h) {
+        const u32x4_t q = resp[i][h];
+        const uint32_t w4[4] = {q.x, q.y, q.z, q.w};
+#pragma unroll
+        for (int e = 0; e < 8; ++e) {
+          const float r = ET::to_f32((uint16_t)((w4[e >> 1] >> ((e & 1) * 16)) & 0xffff));
+          acc[i][2 * h + (e >> 2)][e & 3] += fminf(r, r * inv_slope);
+        }
+      }
+  }
+  __device__ __forceinline__ void add_res(Acc& acc, const u32x2_t (&resq)[MI][NI], float inv_slope) const {
+#pragma unroll
+    for (int i = 0; i < MI; ++i)
+#pragma unroll
+      for (int j = 0; j < NI; ++j) {
+        const float r[4] = {ET::to_f32((uint16_t)(resq[i][j].x & 0xffff)), ET::to_f32((uint16_t)(resq[i][j].x >> 16)),
+                            ET::to_f32((uint16_t)(resq[i][j].y & 0xffff)), ET::to_f32((uint16_t)(resq[i][j].y >> 16))};
+#pragma unroll
+        for (int e = 0; e < 4; ++e) acc[i][j][e] += fminf(r[e], r[e] * inv_slope);
+      }
+  }
+  // t1 = mask(leaky_relu(conv1 + b1)) into the region (the wave rows are level): paired by ds_write_b128, plain by ds_write_b64
+  __device__ __forceinline__ void write_t1(const Acc& acc, int g0, int len, float slope) const {
     u32x2_t t1v[MI][NI];
 #pragma unroll
     for (int i = 0; i < MI; ++i) {
@@ -408,56 +300,111 @@ __global__ __launch_bounds__(512) void respair_phase_kernel(const RpArgs a) {
         for (int j = 0; j < NI; ++j) lds_write_u2(ta + (uint32_t)(((2 * j + (lg >> 1)) ^ (R & 7)) << 4) + (uint32_t)((lg & 1) * 8), t1v[i][j]);
       }
     }
-    init_acc(1);
+  }
+  // output row of conv row r: the rows whose taps stayed inside the tile (`halo` at either end) and inside the clip
+  __device__ __forceinline__ static int64_t out_row(int r, int unit, int g0, int halo, int T) {
+    const int t = g0 + r;
+    return (r >= halo && r < G::RM - halo && t < T) ? (int64_t)unit * T + t : (int64_t)-1;
+  }
+  // Y = leaky_relu(acc) as 16-bit, masked by the clip length: whole 128-byte lines straight from the paired MFMA layout
+  __device__ __forceinline__ void store_y(uint16_t* Y, Acc& acc, int unit, int g0, int halo, int T, int len, float slope) const {
+    auto rowmap = [&](int r) -> int64_t { return out_row(r, unit, g0, halo, T); };
+    l2s_gemm_desc p = {};
+    p.C = Y; p.bias = nullptr; p.N = CH; p.ldc = CH; p.act = L2S_ACT_LRELU; p.act_slope = slope; p.alpha = 1.f;
+    p.mask_T = T; p.mask_mul = 1;
+    int ln = lane;
+    asm volatile("" : "+v"(ln));               // (opaque: the rows and their masks are formed here, not ahead of the tile loop and spilled)
+    epilogue_direct16<ET, MI, NI, L2S_EPI_F16 + 3, decltype(rowmap), NoHook, true>(p, acc, ln, wr * 64, wc * 64, 0, rowmap, unit * T, len);
+  }
+};
+
+// KIND 0: mid pair (Y = leaky_relu(x'));  KIND 1: last pair of a ResBlock (XS (+)= x', optional Y = leaky_relu(XS))
+template <typename ET, int CH, int KIND>
+__global__ __launch_bounds__(512) void respair_phase_kernel(const RpArgs a) {
+  using G = XGeo<CH>;
+  constexpr int MI = 4, NI = 4;
+  constexpr bool PAIRED = KIND == 0;
+  extern __shared__ __attribute__((aligned(16))) uint16_t lds[];
+  const int tid = threadIdx.x;
+  const TileWalk tiles(a.ntiles, a.xcd_order);
+  if (tiles.n <= 0) return;
+  PairCore<ET, CH, PAIRED> pc(lds, tid);
+  const int wr = pc.wr, wc = pc.wc, lm = pc.lm, lg = pc.lg;
+  const int k = a.k, dil = a.dil, h1 = a.h1, h2 = a.h2, T = a.T;
+  const int nkt = k * G::NBLK;               // K-tiles per convolution: (tap, 64-channel block)
+
+  // cursor: the K-tile being staged (uniform pointer to its first half; the second half is 32 weight rows further) - it simply
+  // keeps cycling W1 -> W2 -> W1 ..., so the stagings past the block's last quarter re-fetch the first quarters of W1 into slots
+  // nobody reads (valid memory, exact counts)
+  uint32_t w_lane[G::DPW];
+  pc.lane_offsets(w_lane, k);
+  const uint32_t h_bytes = (uint32_t)(32 * k * CH) * 2u;
+  const char* kt_ptr = (const char*)a.W1;
+  int s_kt = 0, s_conv = 0;
+  auto stage_one = [&](auto dslot_tag, auto sh_tag) {
+    constexpr int DSLOT = decltype(dslot_tag)::value, SH = decltype(sh_tag)::value;
+    pc.template stage_quarter<DSLOT>(kt_ptr + (size_t)(SH ? h_bytes : 0u), w_lane);
+    if constexpr (SH == 1) {
+      kt_ptr += 128;
+      if (++s_kt == nkt) { s_kt = 0; s_conv ^= 1; kt_ptr = (const char*)(s_conv ? a.W2 : a.W1); }
+    }
+  };
+
+  f32x4_t acc[MI][NI];
+  if (tid < 2 * CH) reinterpret_cast<float*>(lds)[G::BIAS_OFF / 4 + tid] = tid < CH ? a.b1[tid] : a.b2[tid - CH];   // stash: b1 | b2
+  __syncthreads();
+  const float slope = a.slope, inv_slope = 1.0f / a.slope;
+  pc.init_acc(acc, 0);
+
+  auto issue_patch = [&](int i) {
+    int unit, g0;
+    tiles.origin(i, a.tiles_per_clip, a.S, h2, unit, g0);
+    pc.issue_patch(a.X, unit, g0, h1, T);
+  };
+  issue_patch(0);
+  stage_one(std::integral_constant<int, 0>{}, std::integral_constant<int, 0>{});
+  stage_one(std::integral_constant<int, 1>{}, std::integral_constant<int, 1>{});
+#ifdef L2S_PAIR_STAMPS
+  unsigned long long pr_acc[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+  unsigned long long pr_last = __builtin_amdgcn_s_memtime();
+  const unsigned long long pr_t0 = pr_last;
+#endif
+  for (int c_i = 0; c_i < tiles.n; ++c_i) {
+    int unit, g0;                              // g0: global time of conv row 0 (t1 row 0 / output row 0)
+    tiles.origin(c_i, a.tiles_per_clip, a.S, h2, unit, g0);
+    int len = a.lens ? a.lens[unit] * a.len_mul : T;
+    len = len < T ? len : T;
+    // ---- tile start (the wave rows are level here): the patch and the first two quarters are visible to every wave ----
+    wait_vmcnt<0>();
+    pc.barrier_then_stagger();
+    PRSTAMP(0)
+    pc.template run_conv<0>(acc, k, dil, h2, stage_one);
+    PRSTAMP(1)
+
+    // ---- conv1 done.  Level the rows, save the residual rows, then t1 into the region ----
+    pc.level();
+    PRSTAMP(7)
+    std::conditional_t<PAIRED, u32x4_t[MI][2], u32x2_t[MI][NI]> res;
+    pc.read_res(res, h1);
+    pc.write_t1(acc, g0, len, slope);
+    pc.init_acc(acc, 1);
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_s_barrier();                          // t1 is visible
-    asm volatile("" ::: "memory");
-    if (upper) __builtin_amdgcn_s_barrier();               // stagger again
+    pc.barrier_then_stagger();                             // t1 is visible
     PRSTAMP(2)
-    run_conv(I1{});
+    pc.template run_conv<1>(acc, k, dil, h2, stage_one);
     PRSTAMP(3)
 
     // ---- conv2 done: level the rows; the region is free once every wave has finished reading t1 ----
-    if (!upper) __builtin_amdgcn_s_barrier();
-    asm volatile("" ::: "memory");
+    pc.level();
     PRSTAMP(5)
     const bool late_patch = (KIND == 1) && a.accumulate;   // that epilogue loads XS: a patch DMA in flight would be drained by it
-    if (!late_patch && c_i + 1 < my_n) issue_patch(c_i + 1);
+    if (!late_patch && c_i + 1 < tiles.n) issue_patch(c_i + 1);
     PRSTAMP(6)
 
-    auto rowmap = [&](int r) -> int64_t {
-      const int t = g0 + r;
-      return (r >= h2 && r < G::RM - h2 && t < T) ? (int64_t)unit * T + t : (int64_t)-1;
-    };
+    pc.add_res(acc, res, inv_slope);                       // x' = conv2 + b2 + x
     if constexpr (KIND == 0) {
-      // x' = conv2 + b2 + x, x recovered from its LeakyReLU'd copy; leaky_relu(x') as 16-bit, whole lines from the MFMA layout
-#pragma unroll
-      for (int i = 0; i < MI; ++i)
-#pragma unroll
-        for (int h = 0; h < 2; ++h) {
-          const u32x4_t q = resp[i][h];
-          const uint32_t w4[4] = {q.x, q.y, q.z, q.w};
-#pragma unroll
-          for (int e = 0; e < 8; ++e) {
-            const float r = ET::to_f32((uint16_t)((w4[e >> 1] >> ((e & 1) * 16)) & 0xffff));
-            acc[i][2 * h + (e >> 2)][e & 3] += fminf(r, r * inv_slope);      // inverse of leaky_relu (slope in (0, 1])
-          }
-        }
-      l2s_gemm_desc p = {};
-      p.C = a.Y; p.bias = nullptr; p.N = CH; p.ldc = CH; p.act = L2S_ACT_LRELU; p.act_slope = slope; p.alpha = 1.f;
-      p.mask_T = T; p.mask_mul = 1;
-      epilogue_direct16<ET, MI, NI, L2S_EPI_F16 + 3, decltype(rowmap), NoHook, true>(p, acc, lane, wr * 64, wc * 64, 0, rowmap,
-                                                                                    unit * T, len);
+      pc.store_y(a.Y, acc, unit, g0, h2, T, len, slope);
     } else {
-#pragma unroll
-      for (int i = 0; i < MI; ++i)
-#pragma unroll
-        for (int j = 0; j < NI; ++j) {
-          const float r[4] = {ET::to_f32((uint16_t)(resq[i][j].x & 0xffff)), ET::to_f32((uint16_t)(resq[i][j].x >> 16)),
-                              ET::to_f32((uint16_t)(resq[i][j].y & 0xffff)), ET::to_f32((uint16_t)(resq[i][j].y >> 16))};
-#pragma unroll
-          for (int e = 0; e < 4; ++e) acc[i][j][e] += fminf(r[e], r[e] * inv_slope);
-        }
       // fp32 sum of the stage's ResBlocks: a lane owns 4 consecutive fp32 channels of its rows (16-byte accesses); the previous
       // sums of TWO row groups are requested up front through unconditional (clamped) addresses (one wait per pair of groups)
       auto do_pair = [&](auto pr_tag) {
@@ -466,7 +413,7 @@ __global__ __launch_bounds__(512) void respair_phase_kernel(const RpArgs a) {
         f32x4_t old[2][NI];
 #pragma unroll
         for (int g2 = 0; g2 < 2; ++g2) {
-          orow[g2] = rowmap(wr * 64 + (2 * pr + g2) * 16 + lm);
+          orow[g2] = pc.out_row(wr * 64 + (2 * pr + g2) * 16 + lm, unit, g0, h2, T);
           const int64_t os = orow[g2] < 0 ? (int64_t)unit * T : orow[g2];
           const float* xs = a.XS + os * CH + wc * 64 + lg * 4;
 #pragma unroll
@@ -503,16 +450,16 @@ __global__ __launch_bounds__(512) void respair_phase_kernel(const RpArgs a) {
       do_pair(std::integral_constant<int, 0>{});
       do_pair(std::integral_constant<int, 1>{});
     }
-    init_acc(0);
-    if (late_patch && c_i + 1 < my_n) issue_patch(c_i + 1);
+    pc.init_acc(acc, 0);
+    if (late_patch && c_i + 1 < tiles.n) issue_patch(c_i + 1);
     PRSTAMP(4)
   }
   wait_vmcnt<0>();                             // no LDS-DMA (the trailing dummies) may outlive the block
 #ifdef L2S_PAIR_STAMPS
-  if (lane == 0 && (wave == 0 || wave == 7) && g_pair_stamps) {
-    unsigned long long* o = g_pair_stamps + ((int64_t)blockIdx.x * 2 + (wave ? 1 : 0)) * 16;
+  if (pc.lane == 0 && (pc.wave == 0 || pc.wave == 7) && g_pair_stamps) {
+    unsigned long long* o = g_pair_stamps + ((int64_t)blockIdx.x * 2 + (pc.wave ? 1 : 0)) * 16;
     for (int i = 0; i < 8; ++i) o[i] = pr_acc[i];
-    o[8] = (unsigned long long)my_n;
+    o[8] = (unsigned long long)tiles.n;
     o[9] = __builtin_amdgcn_s_memtime() - pr_t0;
   }
 #endif
@@ -527,94 +474,39 @@ __global__ __launch_bounds__(512) void respair_phase_kernel(const RpArgs a) {
 // conv2) while conv1 uses a second set: 128 accumulator + 48 fragment registers.  The stage sum never exists in HBM: the only
 // output is Y = leaky_relu(sum) in 16 bits (every wide stage feeds leaky_relu + ups next, models.py:109,101; a stage whose fp32
 // sum is read - the last one - keeps the per-pair launches).  Tiles are cut for the largest k (S = RM - 2 h2max); the weight
-// stream runs W1_0, W2_0, W1_1, ... across the j loop and the tiles; everything else is respair_phase_kernel's mid-pair path
-// (paired W order, t1 by ds_write_b128, whole-line 16-bit epilogue).
+// stream runs W1_0, W2_0, W1_1, ... across the j loop and the tiles; everything else is PairCore's paired path, as in a mid pair.
 template <typename ET, int CH>
 __global__ __launch_bounds__(512) void respair_final_kernel(const l2s_rp::RpFinalArgs a) {
   using G = XGeo<CH>;
   constexpr int MI = 4, NI = 4;
   extern __shared__ __attribute__((aligned(16))) uint16_t lds[];
-  const int tid = threadIdx.x, lane = tid & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int wr = wave / G::NWC, wc = wave % G::NWC;
-  const bool upper = wave >= 4;
-  const int lm = lane & 15, lg = lane >> 4;
-  const int srow = lane >> 3, schunk = (lane & 7) ^ (srow & 7);
+  const int tid = threadIdx.x;
+  const TileWalk tiles(a.ntiles, a.xcd_order);
+  if (tiles.n <= 0) return;
+  PairCore<ET, CH, true> pc(lds, tid);
   const int T = a.T, nj = a.nj, h2max = a.h2max;
-  const uint16_t* zero = reinterpret_cast<const uint16_t*>(&g_zero16);
   auto kof = [&](int j) { return j == 0 ? a.k[0] : (j == 1 ? a.k[1] : a.k[2]); };
   auto dof = [&](int j) { return j == 0 ? a.dil[0] : (j == 1 ? a.dil[1] : a.dil[2]); };
   auto xof = [&](int j) { return j == 0 ? a.X[0] : (j == 1 ? a.X[1] : a.X[2]); };
   auto w1of = [&](int j) { return j == 0 ? a.W1[0] : (j == 1 ? a.W1[1] : a.W1[2]); };
   auto w2of = [&](int j) { return j == 0 ? a.W2[0] : (j == 1 ? a.W2[1] : a.W2[2]); };
 
-  int my_n = 0;
-  if (!a.xcd_order) {
-    my_n = (a.ntiles - (int)blockIdx.x + (int)gridDim.x - 1) / (int)gridDim.x;
-  } else {
-    const int per = (a.ntiles + 7) >> 3, lo = ((int)blockIdx.x & 7) * per;
-    int hi = lo + per;
-    hi = hi < a.ntiles ? hi : a.ntiles;
-    const int gxx = ((int)gridDim.x + 7) >> 3, b8 = (int)blockIdx.x >> 3;
-    if (lo + b8 < hi) my_n = (hi - lo - b8 + gxx - 1) / gxx;
-  }
-  if (my_n <= 0) return;
-  const int xcd = blockIdx.x & 7, bx = blockIdx.x >> 3, gx = (gridDim.x + 7) >> 3;
-  const int per_xcd = (a.ntiles + 7) >> 3;
-  auto tile_origin = [&](int i, int& unit, int& g0) {
-    const int L = a.xcd_order ? xcd * per_xcd + bx + i * gx : (int)blockIdx.x + i * (int)gridDim.x;
-    unit = L / a.tiles_per_clip;
-    g0 = (L - unit * a.tiles_per_clip) * a.S - h2max;   // global time of conv row 0, the same for every ResBlock of the tile
-  };
-  const uint32_t lds_base = (uint32_t)(uintptr_t)(lptr_t)lds;
-  const uint32_t wring = lds_base + G::REGION;
-
-  // patch of ResBlock j for tile i
+  // patch of ResBlock j for tile i (g0, the global time of conv row 0, is the same for every ResBlock of the tile)
   auto issue_patch = [&](int i, int j) {
     int unit, g0;
-    tile_origin(i, unit, g0);
-    const int h1 = ((kof(j) - 1) / 2) * dof(j);
-    const int patch_rows = G::RM + 2 * h1;
-    const uint16_t* X = xof(j);
-#pragma unroll
-    for (int q = 0; q < G::PPW; ++q) {
-      const int instr = wave * G::PPW + q;
-      const int cq = instr / (G::RPR / 8), blk = instr - cq * (G::RPR / 8);
-      if (instr < G::PI && blk * 8 < patch_rows) {
-        const int ts = g0 - h1 + blk * 8 + srow;
-        const uint16_t* g = ((unsigned)ts < (unsigned)T) ? X + ((int64_t)unit * T + ts) * CH + cq * 64 + schunk * 8 : zero;
-        __builtin_amdgcn_global_load_lds((gptr_t)g, (lptr_t)(lds + cq * (G::BLK_B / 2) + blk * 512), 16, 0, 0);
-      }
-    }
+    tiles.origin(i, a.tiles_per_clip, a.S, h2max, unit, g0);
+    pc.issue_patch(xof(j), unit, g0, ((kof(j) - 1) / 2) * dof(j), T);
   };
 
-  // ---- weight stream: W1_0, W2_0, W1_1, W2_1, ... cycling; the per-lane byte offset depends on k_j (row pitch k_j * CH) ----
-  const bool stager = CH >= 128 || !(wave & 1);
-  const int sw = CH >= 128 ? wave : wave >> 1;
-  uint32_t w_row[G::DPW], w_chunk[G::DPW], w_lane[G::DPW];
-#pragma unroll
-  for (int q = 0; q < G::DPW; ++q) {
-    const int qrow = sw * G::RPS + 8 * q + srow;
-    const int within = qrow & 31;
-    w_row[q] = (uint32_t)((qrow >> 5) * 64 + within);
-    w_chunk[q] = (uint32_t)(((lane & 7) ^ paired_w_key(within)) * 16);
-  }
+  // ---- weight cursor: W1_0, W2_0, W1_1, W2_1, ... cycling; the per-lane byte offset depends on k_j (row pitch k_j * CH) ----
+  uint32_t w_lane[G::DPW];
   int s_j = 0, s_conv = 0, s_kt = 0, s_nkt = kof(0) * G::NBLK;
   uint32_t h_bytes = (uint32_t)(64 * kof(0) * CH);          // 32 weight rows further
   const char* kt_ptr = (const char*)a.W1[0];
-  auto set_lane_offsets = [&]() {
-    const uint32_t pitch = (uint32_t)(kof(s_j) * CH * 2);
-#pragma unroll
-    for (int q = 0; q < G::DPW; ++q) w_lane[q] = w_row[q] * pitch + w_chunk[q];
-  };
-  set_lane_offsets();
+  pc.lane_offsets(w_lane, kof(0));
   auto stage_one = [&](auto dslot_tag, auto sh_tag) {
     constexpr int DSLOT = decltype(dslot_tag)::value, SH = decltype(sh_tag)::value;
-    const char* wb = kt_ptr + (size_t)(SH ? h_bytes : 0u);
-    uint16_t* dst = lds + G::REGION / 2 + DSLOT * (G::Q_B / 2) + sw * G::RPS * 64;
-#pragma unroll
-    for (int q = 0; q < G::DPW; ++q)
-      if (stager) __builtin_amdgcn_global_load_lds((gptr_t)(wb + (size_t)w_lane[q]), (lptr_t)(dst + q * 512), 16, 0, 0);
+    pc.template stage_quarter<DSLOT>(kt_ptr + (size_t)(SH ? h_bytes : 0u), w_lane);
     if constexpr (SH == 1) {
       kt_ptr += 128;
       if (++s_kt == s_nkt) {
@@ -628,37 +520,14 @@ __global__ __launch_bounds__(512) void respair_final_kernel(const l2s_rp::RpFina
           s_nkt = kof(s_j) * G::NBLK;
           h_bytes = (uint32_t)(64 * kof(s_j) * CH);
           kt_ptr = (const char*)w1of(s_j);
-          set_lane_offsets();
+          pc.lane_offsets(w_lane, kof(s_j));
         }
       }
     }
   };
 
-  // ---- fragments (paired W order) ----
-  uint32_t wP, wQ;
-  {
-    const int row0 = 8 * (lm >> 2) + (lm & 3);
-    const int c0 = lg ^ paired_w_key(row0);
-    wP = wring + (uint32_t)(wc * 4096 + row0 * 128 + (c0 << 4));
-    wQ = wring + (uint32_t)(wc * 4096 + row0 * 128 + ((c0 ^ 4) << 4));
-  }
-  frag16 fa[MI][2], fb[2][2];
-  auto read_b = [&](auto slot_tag) {
-    constexpr int SO = decltype(slot_tag)::value * G::Q_B;
-    lds_read_b128<SO>(fb[0][0], wP); lds_read_b128<SO + 512>(fb[1][0], wQ);
-    lds_read_b128<SO>(fb[0][1], wQ); lds_read_b128<SO + 512>(fb[1][1], wP);
-  };
-  auto read_a = [&](auto off_tag, uint32_t a0, uint32_t a1) {
-    constexpr int AO = decltype(off_tag)::value;
-    lds_read_b128<AO>(fa[0][0], a0); lds_read_b128<AO + 2048>(fa[1][0], a0); lds_read_b128<AO + 4096>(fa[2][0], a0); lds_read_b128<AO + 6144>(fa[3][0], a0);
-    lds_read_b128<AO>(fa[0][1], a1); lds_read_b128<AO + 2048>(fa[1][1], a1); lds_read_b128<AO + 4096>(fa[2][1], a1); lds_read_b128<AO + 6144>(fa[3][1], a1);
-  };
-
   f32x4_t acc1[MI][NI], sum[MI][NI];
   // LDS stash behind the ring: b1_0 | b1_1 | b1_2 | b2_0 + b2_1 + b2_2, CH floats each
-  uint32_t bias_ad[NI];
-#pragma unroll
-  for (int j = 0; j < NI; ++j) bias_ad[j] = lds_base + G::BIAS_OFF + (uint32_t)((wc * 64 + 32 * (j >> 1) + 8 * lg + 4 * (j & 1)) * 4);
   for (int i = tid; i < 4 * CH; i += 512) {
     const int j = i / CH, c = i - j * CH;
     float v = 0.f;
@@ -667,181 +536,44 @@ __global__ __launch_bounds__(512) void respair_final_kernel(const l2s_rp::RpFina
     reinterpret_cast<float*>(lds)[G::BIAS_OFF / 4 + i] = v;
   }
   __syncthreads();
-  auto init_acc = [&](f32x4_t (&accx)[MI][NI], const int which) {
-    uint32_t ad[4];
-#pragma unroll
-    for (int j = 0; j < NI; ++j) ad[j] = bias_ad[j] + (uint32_t)(which * CH * 4);
-    f32x4_t bj[NI];
-    lds_read4_f4_sync(bj, ad);
-#pragma unroll
-    for (int i = 0; i < MI; ++i)
-#pragma unroll
-      for (int j = 0; j < NI; ++j) accx[i][j] = bj[j];
-  };
-
-  auto phase = [&](f32x4_t (&accx)[MI][NI], auto h_tag, auto slot_tag, auto aoff_tag, uint32_t a0, uint32_t a1) {
-    constexpr int H = decltype(h_tag)::value, SLOT = decltype(slot_tag)::value;
-    read_b(slot_tag);
-    if (H == 0) { __builtin_amdgcn_sched_barrier(0); read_a(aoff_tag, a0, a1); }
-    stage_one(std::integral_constant<int, (SLOT + 2) & (XRQ - 1)>{}, h_tag);
-    __builtin_amdgcn_sched_barrier(0);
-    wait_vmcnt<G::DPW>();
-    asm volatile("" ::: "memory");
-    __builtin_amdgcn_s_barrier();
-    asm volatile("" ::: "memory");
-    lds_wait();
-    __builtin_amdgcn_s_setprio(1);
-#pragma unroll
-    for (int i = 0; i < MI; ++i)
-#pragma unroll
-      for (int s2 = 0; s2 < 2; ++s2) {
-        accx[i][2 * H + s2] = ET::mfma(fb[s2][0], fa[i][0], accx[i][2 * H + s2]);
-        accx[i][2 * H + s2] = ET::mfma(fb[s2][1], fa[i][1], accx[i][2 * H + s2]);
-      }
-    __builtin_amdgcn_s_setprio(0);
-    __builtin_amdgcn_sched_barrier(0);
-    asm volatile("" ::: "memory");
-    __builtin_amdgcn_s_barrier();
-    asm volatile("" ::: "memory");
-    __builtin_amdgcn_sched_barrier(0);
-  };
-  using I0 = std::integral_constant<int, 0>; using I1 = std::integral_constant<int, 1>;
-  using I2 = std::integral_constant<int, 2>; using I3 = std::integral_constant<int, 3>;
-  using IB = std::integral_constant<int, G::BLK_B>;
-  int k = 0, dil = 0, h2 = 0;      // of the ResBlock being computed
-  auto run_conv = [&](auto conv_tag, f32x4_t (&accx)[MI][NI]) {
-    constexpr int conv = decltype(conv_tag)::value;
-    auto row_addr = [&](int tap, uint32_t& a0, uint32_t& a1) {
-      const int pr = wr * 64 + lm + (conv == 0 ? tap * dil : tap - h2 + XT1);
-      const int x = pr & 7;
-      const uint32_t pa = lds_base + (uint32_t)pr * 128;
-      a0 = pa + (uint32_t)(((0 + lg) ^ x) << 4);
-      a1 = pa + (uint32_t)(((4 + lg) ^ x) << 4);
-    };
-    if constexpr (CH == 64) {
-      using SA = std::integral_constant<int, conv ? 2 : 0>; using SB = std::integral_constant<int, conv ? 3 : 1>;
-      using SC = std::integral_constant<int, conv ? 0 : 2>; using SD = std::integral_constant<int, conv ? 1 : 3>;
-      int tap = 0;
-      for (; tap + 1 < k; tap += 2) {
-        uint32_t a0, a1, c0, c1;
-        row_addr(tap, a0, a1);
-        row_addr(tap + 1, c0, c1);
-        phase(accx, I0{}, SA{}, I0{}, a0, a1); phase(accx, I1{}, SB{}, I0{}, 0u, 0u);
-        phase(accx, I0{}, SC{}, I0{}, c0, c1); phase(accx, I1{}, SD{}, I0{}, 0u, 0u);
-      }
-      uint32_t a0, a1;
-      row_addr(tap, a0, a1);
-      phase(accx, I0{}, SA{}, I0{}, a0, a1); phase(accx, I1{}, SB{}, I0{}, 0u, 0u);
-    } else {
-      for (int tap = 0; tap < k; ++tap) {
-        uint32_t a0, a1;
-        row_addr(tap, a0, a1);
-        phase(accx, I0{}, I0{}, I0{}, a0, a1); phase(accx, I1{}, I1{}, I0{}, 0u, 0u);
-        phase(accx, I0{}, I2{}, IB{}, a0, a1); phase(accx, I1{}, I3{}, I0{}, 0u, 0u);
-        if constexpr (CH == 256) {
-          const uint32_t c0 = a0 + 2 * G::BLK_B, c1 = a1 + 2 * G::BLK_B;
-          phase(accx, I0{}, I0{}, I0{}, c0, c1); phase(accx, I1{}, I1{}, I0{}, 0u, 0u);
-          phase(accx, I0{}, I2{}, IB{}, c0, c1); phase(accx, I1{}, I3{}, I0{}, 0u, 0u);
-        }
-      }
-    }
-  };
 
   const float slope = a.slope, inv_slope = 1.0f / a.slope;
   issue_patch(0, 0);
-  stage_one(I0{}, I0{});
-  stage_one(I1{}, I1{});
-  for (int c_i = 0; c_i < my_n; ++c_i) {
+  stage_one(std::integral_constant<int, 0>{}, std::integral_constant<int, 0>{});
+  stage_one(std::integral_constant<int, 1>{}, std::integral_constant<int, 1>{});
+  for (int c_i = 0; c_i < tiles.n; ++c_i) {
     int unit, g0;
-    tile_origin(c_i, unit, g0);
+    tiles.origin(c_i, a.tiles_per_clip, a.S, h2max, unit, g0);
     int len = a.lens ? a.lens[unit] * a.len_mul : T;
     len = len < T ? len : T;
     for (int j = 0; j < nj; ++j) {
-      k = kof(j); dil = dof(j); h2 = (k - 1) / 2;
-      const int h1 = h2 * dil;
+      const int k = kof(j), dil = dof(j), h2 = (k - 1) / 2, h1 = h2 * dil;
       // ---- ResBlock j of the tile: its patch and the next quarters are visible to every wave (the wave rows are level here) ----
-      init_acc(acc1, j);
-      if (j == 0) init_acc(sum, 3);
+      pc.init_acc(acc1, j);
+      if (j == 0) pc.init_acc(sum, 3);
       wait_vmcnt<0>();
-      __builtin_amdgcn_s_barrier();
-      asm volatile("" ::: "memory");
-      if (upper) __builtin_amdgcn_s_barrier();
-      run_conv(I0{}, acc1);
+      pc.barrier_then_stagger();
+      pc.template run_conv<0>(acc1, k, dil, h2, stage_one);
 
       // ---- conv1 done: level the rows; sum += x_j (recovered from the LeakyReLU'd patch rows); t1 = mask(leaky_relu(conv1 + b1)) ----
-      if (!upper) __builtin_amdgcn_s_barrier();
-      asm volatile("" ::: "memory");
+      pc.level();
       {
         u32x4_t resp[MI][2];
-        uint32_t ad[MI][2];
-#pragma unroll
-        for (int i = 0; i < MI; ++i) {
-          const int R = wr * 64 + i * 16 + lm + h1;
-          const uint32_t ra = lds_base + (uint32_t)wc * G::BLK_B + (uint32_t)R * 128;
-          ad[i][0] = ra + (uint32_t)(((0 + lg) ^ (R & 7)) << 4);
-          ad[i][1] = ra + (uint32_t)(((4 + lg) ^ (R & 7)) << 4);
-        }
-        lds_read8_u4_sync(resp, ad);
-#pragma unroll
-        for (int i = 0; i < MI; ++i)
-#pragma unroll
-          for (int h = 0; h < 2; ++h) {
-            const u32x4_t q = resp[i][h];
-            const uint32_t w4[4] = {q.x, q.y, q.z, q.w};
-#pragma unroll
-            for (int e = 0; e < 8; ++e) {
-              const float r = ET::to_f32((uint16_t)((w4[e >> 1] >> ((e & 1) * 16)) & 0xffff));
-              sum[i][2 * h + (e >> 2)][e & 3] += fminf(r, r * inv_slope);
-            }
-          }
+        pc.read_res(resp, h1);
+        pc.add_res(sum, resp, inv_slope);
       }
-      u32x2_t t1v[MI][NI];
-#pragma unroll
-      for (int i = 0; i < MI; ++i) {
-        const int t = g0 + wr * 64 + i * 16 + lm;
-        const uint32_t km = (unsigned)t < (unsigned)len ? 0xffffffffu : 0u;
-#pragma unroll
-        for (int jj = 0; jj < NI; ++jj) {
-          f32x4_t v = acc1[i][jj];
-          const f32x4_t sc = v * slope;
-#pragma unroll
-          for (int e = 0; e < 4; ++e) v[e] = fmaxf(v[e], sc[e]);
-          t1v[i][jj].x = ET::pack2(v[0], v[1]) & km;
-          t1v[i][jj].y = ET::pack2(v[2], v[3]) & km;
-        }
-      }
-      __builtin_amdgcn_s_barrier();                        // every wave is done reading the patch
-      asm volatile("" ::: "memory");
-#pragma unroll
-      for (int i = 0; i < MI; ++i) {
-        const int R = wr * 64 + i * 16 + lm + XT1;
-        const uint32_t ta = lds_base + (uint32_t)wc * G::BLK_B + (uint32_t)R * 128;
-#pragma unroll
-        for (int h = 0; h < 2; ++h)
-          lds_write_u4(ta + (uint32_t)(((4 * h + lg) ^ (R & 7)) << 4),
-                       u32x4_t{t1v[i][2 * h].x, t1v[i][2 * h].y, t1v[i][2 * h + 1].x, t1v[i][2 * h + 1].y});
-      }
+      pc.write_t1(acc1, g0, len, slope);
       asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-      __builtin_amdgcn_s_barrier();                        // t1 is visible
-      asm volatile("" ::: "memory");
-      if (upper) __builtin_amdgcn_s_barrier();
-      run_conv(I1{}, sum);
+      pc.barrier_then_stagger();                           // t1 is visible
+      pc.template run_conv<1>(sum, k, dil, h2, stage_one);
 
       // ---- conv2 done: level the rows; the region is free: the next ResBlock's (or the next tile's) patch travels now ----
-      if (!upper) __builtin_amdgcn_s_barrier();
-      asm volatile("" ::: "memory");
+      pc.level();
       if (j + 1 < nj) issue_patch(c_i, j + 1);
-      else if (c_i + 1 < my_n) issue_patch(c_i + 1, 0);
+      else if (c_i + 1 < tiles.n) issue_patch(c_i + 1, 0);
     }
     // ---- Y = leaky_relu(sum) for the rows whose taps stayed inside the tile for EVERY ResBlock, masked by the clip length ----
-    auto rowmap = [&](int r) -> int64_t {
-      const int t = g0 + r;
-      return (r >= h2max && r < G::RM - h2max && t < T) ? (int64_t)unit * T + t : (int64_t)-1;
-    };
-    l2s_gemm_desc p = {};
-    p.C = a.Y; p.bias = nullptr; p.N = CH; p.ldc = CH; p.act = L2S_ACT_LRELU; p.act_slope = slope; p.alpha = 1.f;
-    p.mask_T = T; p.mask_mul = 1;
-    epilogue_direct16<ET, MI, NI, L2S_EPI_F16 + 3, decltype(rowmap), NoHook, true>(p, sum, lane, wr * 64, wc * 64, 0, rowmap, unit * T, len);
+    pc.store_y(a.Y, sum, unit, g0, h2max, T, len, slope);
   }
   wait_vmcnt<0>();
 }

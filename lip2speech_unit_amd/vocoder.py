@@ -21,7 +21,7 @@ from .packing import convtranspose_fused, convtranspose_phases, pack_conv1d
 LRELU_SLOPE = 0.1  # speech-resynthesis/models.py:13
 # C = 64 / 128 stages: one launch per (c1, c2) conv pair out of LDS (csrc/respair.hip); 0 = the unfused tap-GEMM pairs (A/B)
 FUSED_PAIR = os.environ.get("L2S_RESPAIR", "1") != "0"
-# ... and the C = 256 stage on the phase-staggered pair kernel (csrc/respair256.hip); 0 = its 18 tap-GEMM launches (A/B)
+# ... and the C = 256 stage on the phase-staggered pair kernel (csrc/respair_phase.hip); 0 = its 18 tap-GEMM launches (A/B)
 FUSED_PAIR256 = os.environ.get("L2S_RESPAIR256", "1") != "0"
 # The pair kernels walk B * ceil(T / rows) time tiles, one per CU (rows = 128 / 256 / 512 at C = 256 / 128 / 64).  With fewer than
 # PAIR_MIN_TILES of them - one clip per request: 16-40 tiles - a pair is two K loops in a row on a handful of CUs and the tap-GEMM

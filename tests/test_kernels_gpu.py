@@ -17,6 +17,22 @@ def _r16(x, dt):
     return x.to(ops.torch_dtype(dt)).float()
 
 
+def _over_256_tiles(C):
+    """(T, lens) of a batch that the phase-staggered conv-pair kernels (csrc/respair_phase.hip) cut into MORE than 256 tiles at
+    k = 11 (S = RM - 10 rows per tile).  Their grid is min(round_up(ntiles, 8), 256) blocks, so only then a block walks a SECOND
+    tile: the weight cursor wraps W2 -> W1, the next tile's patch is issued under the epilogue, the accumulators are re-seeded.
+    In XCD order block (xcd, bx) of 8 x 32 takes the tiles L = xcd * per + bx + 32 i, per = ceil(ntiles / 8); the second ones:
+      C = 256: RM 128, S 118, T 1700: 15 tiles per clip x 18 clips = 270, per 34: L = 34 xcd + 32, + 33 = 32, 33, 66, 67, ...
+               = clips 2, 2, 4, 4, 6, 6, 8, 9, 11, 11, 13, 13, 15, 15            full length: 2, 9, 15 (five second tiles)
+      C = 128: RM 256, S 246, T 1900:  8 x 33 = 264, per 33: L = 33 xcd + 32 = tile xcd of clip 4 + 4 xcd     full: 4, 12, 20, 32
+      C =  64: RM 512, S 502, T 1900:  4 x 65 = 260, per 33: L = 33 xcd + 32, xcd < 7 (263 is past the end)
+               = clips 8, 16, 24, 32, 41, 49, 57                                 full: 8, 16, 32, 57
+    Tiles exist whatever `lens` says, so every other clip is short (the CPU reference runs over the valid rows only)."""
+    T, B, S, full = {256: (1700, 18, 118, (2, 9, 15)), 128: (1900, 33, 246, (4, 12, 20, 32)), 64: (1900, 65, 502, (8, 16, 32, 57))}[C]
+    short = (0, 1, S - 1, S, S + 1, 17)
+    return T, [T if b in full else short[b % len(short)] for b in range(B)]
+
+
 @pytest.mark.parametrize("dt", [ops.F16, ops.BF16])
 @pytest.mark.parametrize("M,C,zp,eps", [(37, 1024, 0, 1e-5), (50, 512, 0, 1e-12), (21, 1024, 1024, 1e-5), (9, 2048, 0, 1e-5)])
 def test_layernorm(dt, M, C, zp, eps):
@@ -628,15 +644,9 @@ def test_stem_pool_fused_vs_torch(slopes, dt, tol):
     assert err <= tol * ref.abs().max().item(), (err, ref.abs().max().item())
 
 
-@pytest.mark.parametrize("dt", [ops.F16, ops.BF16])
-@pytest.mark.parametrize("C,T,lens", [(256, 300, [300, 211, 0]), (128, 700, [700, 246, 245]), (64, 1100, [1100, 502, 1]),
-                                      (256, 117, [117, 118 - 1, 1])])
-def test_respair_final_equals_the_last_pairs_summed(dt, C, T, lens):
-    """l2s_respair_final (the last (c1, c2, d = 5) pairs of a stage's three ResBlocks, k = 3 / 7 / 11, in one launch with the stage
-    sum in accumulators) against (a) torch fp32 on each clip alone and (b) the three l2s_respair(last) launches it replaces
-    (same kernels' arithmetic; only the order of the fp32 additions of the sum differs)."""
+def _respair_final_case(dt, C, T, lens, ks):
     t16 = ops.torch_dtype(dt)
-    B, slope, ks, dil = len(lens), 0.1, (3, 7, 11), 5
+    B, slope, dil = len(lens), 0.1, 5
     g = torch.Generator().manual_seed(C + T)
     L = torch.tensor(lens, dtype=torch.int32)
     valid = torch.arange(T)[None, :] < L[:, None]
@@ -662,7 +672,7 @@ def test_respair_final_equals_the_last_pairs_summed(dt, C, T, lens):
         b2s.append(b2.cuda())
     kw = dict(B=B, T=T, C=C, slope=slope, lens=L.cuda(), len_mul=1, dtype=dt)
     y = torch.full((B * T, C), 7.0, device="cuda", dtype=t16)
-    ops.respair_final(xs_l, w1s, b1s, w2s, b2s, y, ks=list(ks), dils=[dil] * 3, **kw)
+    ops.respair_final(xs_l, w1s, b1s, w2s, b2s, y, ks=list(ks), dils=[dil] * len(ks), **kw)
     got = y.float().cpu().view(B, T, C)
     want = F.leaky_relu(ref, slope)
     tol = (3e-3 if dt == ops.F16 else 2e-2) * ref.abs().max().item()
@@ -673,12 +683,33 @@ def test_respair_final_equals_the_last_pairs_summed(dt, C, T, lens):
     xs = torch.zeros(B * T, C, device="cuda")
     y2 = torch.full((B * T, C), 7.0, device="cuda", dtype=t16)
     for j, k in enumerate(ks):
-        ops.respair(xs_l[j], w1s[j], b1s[j], w2s[j], b2s[j], k=k, dil=dil, xs=xs, y=y2 if j == 2 else None, accumulate=j > 0, **kw)
+        ops.respair(xs_l[j], w1s[j], b1s[j], w2s[j], b2s[j], k=k, dil=dil, xs=xs, y=y2 if j == len(ks) - 1 else None, accumulate=j > 0, **kw)
     torch.cuda.synchronize()
     d = (y.float() - y2.float()).abs().max().item()
     assert d <= (2e-3 if dt == ops.F16 else 1.6e-2) * ref.abs().max().item(), d
+    return xs_l, w1s, b1s, w2s, b2s, y, kw
+
+
+@pytest.mark.parametrize("dt", [ops.F16, ops.BF16])
+@pytest.mark.parametrize("C,T,lens", [(256, 300, [300, 211, 0]), (128, 700, [700, 246, 245]), (64, 1100, [1100, 502, 1]),
+                                      (256, 117, [117, 118 - 1, 1]),
+                                      # more than 256 tiles: a block walks a second tile
+                                      (256,) + _over_256_tiles(256), (128,) + _over_256_tiles(128), (64,) + _over_256_tiles(64)])
+def test_respair_final_equals_the_last_pairs_summed(dt, C, T, lens):
+    """l2s_respair_final (the last (c1, c2, d = 5) pairs of a stage's three ResBlocks, k = 3 / 7 / 11, in one launch with the stage
+    sum in accumulators) against (a) torch fp32 on each clip alone and (b) the three l2s_respair(last) launches it replaces
+    (same kernels' arithmetic; only the order of the fp32 additions of the sum differs)."""
+    xs_l, w1s, b1s, w2s, b2s, y, kw = _respair_final_case(dt, C, T, lens, (3, 7, 11))
     with pytest.raises(ops.L2SError):      # a fourth ResBlock is not built
         ops.respair_final(xs_l + xs_l[:1], w1s + w1s[:1], b1s + b1s[:1], w2s + w2s[:1], b2s + b2s[:1], y, ks=[3, 7, 11, 3], dils=[5] * 4, **kw)
+
+
+@pytest.mark.parametrize("dt", [ops.F16, ops.BF16])
+@pytest.mark.parametrize("ks", [(11,), (7, 3)])
+def test_respair_final_one_and_two_resblocks(dt, ks):
+    """l2s_respair_final with n = 1 and n = 2 ResBlocks at C = 64 (tiles cut for the largest k; the weight cursor returns to W1_0
+    after W2_{n-1}): the same two references as above."""
+    _respair_final_case(dt, 64, 1100, [1100, 502, 1], ks)
 
 
 @pytest.mark.parametrize("slopes", ["positive", "mixed"])
@@ -910,12 +941,15 @@ def test_resstage_fused_rejects_other_layouts():
                                             # edge cases: clip shorter than one tile / than the halo, an empty clip, one sample
                                             (64, 11, 5, 33, [33, 0, 7]), (128, 3, 1, 1, [1, 1]), (64, 7, 5, 191, [0, 191]),
                                             (128, 7, 3, 187, [187, 186, 185, 1]),
-                                            # C = 256: csrc/respair256.hip (128-row tiles, phase-staggered weight stream)
+                                            # C = 256: csrc/respair_phase.hip (128-row tiles, phase-staggered weight stream)
                                             (256, 3, 1, 300, [300, 211]), (256, 7, 3, 257, [257, 40]), (256, 11, 5, 400, [400, 399]),
                                             (256, 11, 1, 2000, [2000, 1999, 1217]), (256, 7, 5, 119, [119, 0, 1]),
                                             (256, 3, 5, 1, [1, 1]), (256, 11, 3, 129, [128, 129, 118, 117]),
                                             # C = 128 takes the same kernel with 256-row tiles: lengths around the tile edges
-                                            (128, 11, 5, 600, [600, 246, 247, 245]), (128, 3, 3, 257, [257, 256, 254, 0])])
+                                            (128, 11, 5, 600, [600, 246, 247, 245]), (128, 3, 3, 257, [257, 256, 254, 0]),
+                                            # more than 256 tiles: a block walks a second tile
+                                            (256, 11, 5) + _over_256_tiles(256), (128, 11, 5) + _over_256_tiles(128),
+                                            (64, 11, 5) + _over_256_tiles(64)])
 def test_respair_fused_conv_pair(dt, C, k, dil, T, lens):
     """csrc/respair.hip against torch fp32 on each clip ALONE: x' = c2(lrelu(c1(lrelu(x)))) + x with the input / output
     carried as LeakyReLU'd 16-bit copies; mid pair, last pair (overwrite, accumulate, with and without the second output)."""

@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
-"""Micro-benchmark of the fused conv pairs (csrc/respair.hip C = 64 / 128, csrc/respair256.hip C = 256) at the vocoder's
+"""Micro-benchmark of the fused conv pairs (csrc/respair.hip C = 64 / 128, csrc/respair_phase.hip C = 256) at the vocoder's
 shapes, launched as the pipeline launches them: per (C, k) the two mid pairs (dil 1, 3) and the last pair (dil 5, accumulate
-into the fp32 ResBlock sum).  With `unfused` the C = 256 stage is also timed as its tap-GEMM launches (the path until round 4).
+into the fp32 ResBlock sum), then the one launch that replaces the three last pairs (l2s_respair_final: three ResBlocks,
+k = 3 / 7 / 11, dil 5).  With `unfused` the C = 256 stage is also timed as its tap-GEMM launches (the path until round 4).
 usage: python tools/pair_bench.py [B] [C ...] [unfused]      (L2S_LIB_PATH selects an A/B build of the library)"""
 import os
 import sys
@@ -40,10 +41,12 @@ for C in Cs:
     lens = torch.full((B,), T, dtype=torch.int32, device="cuda")
     tot = 0.0
     tot_fl = 0.0
+    w1s, w2s, b1s, b2s = [], [], [], []
     for k in (3, 7, 11):
         w1 = (torch.randn(C, k * C, device="cuda") / (k * C) ** 0.5).half()
         w2 = (torch.randn(C, k * C, device="cuda") / (k * C) ** 0.5).half()
         b1, b2 = torch.randn(C, device="cuda") * 0.1, torch.randn(C, device="cuda") * 0.1
+        w1s.append(w1); w2s.append(w2); b1s.append(b1); b2s.append(b2)
         fl = 2 * 2.0 * M * C * C * k
         row = []
         for dil, kind in ((1, "mid"), (3, "mid"), (5, "last")):
@@ -58,6 +61,10 @@ for C in Cs:
             row.append(f"{kind} d{dil} {us:8.1f} us {fl / us * 1e-6:6.0f} TF")
         print(f"C{C} k{k:2d}: " + "   ".join(row), flush=True)
     print(f"C{C} stage (9 pairs): {tot / 1e3:8.3f} ms per {B} clips   {tot_fl / tot * 1e-6:6.0f} TFLOP/s", flush=True)
+    us = timeit(lambda: ops.respair_final([xl] * 3, w1s, b1s, w2s, b2s, y, B=B, T=T, C=C, ks=[3, 7, 11], dils=[5] * 3, slope=0.1,
+                                          lens=lens, len_mul=1))
+    fl = sum(2 * 2.0 * M * C * C * k for k in (3, 7, 11))
+    print(f"C{C} respair_final (3 last pairs, one launch): {us:8.1f} us {fl / us * 1e-6:6.0f} TF", flush=True)
     if unfused and C == 256:
         t1 = torch.empty(M, C, device="cuda", dtype=torch.float16)
         o = torch.empty(M, C, device="cuda", dtype=torch.float16)
