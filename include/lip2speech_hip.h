@@ -504,6 +504,40 @@ int l2s_ctc_loss(const float* logits, int ldl, const int32_t* lens, int len_mul,
                  const int32_t* targets, const int32_t* tgt_lens, const int32_t* tgt_offs, int S_max, void* workspace,
                  size_t workspace_bytes, float* nll, void* stream);
 
+/*
+ * Speech units from audio (extract_speech_units.sh:6-11: HuBERT-base features of transformer layer 6, quantised by a k-means
+ * model).  Two entries; the rest of the path runs on l2s_tapgemm, l2s_layernorm and l2s_attention.
+ *
+ * l2s_wave_stem - layer 0 of fairseq's ConvFeatureExtractionModel in mode="default" (fairseq is not in the reference tree; the
+ * script above loads it through hubert_base_ls960.pt), csrc/wavestem.hip:
+ *   Conv1d(1 -> C, k = 10, stride 5, no bias), GroupNorm(C groups, C channels, affine, eps), erf GELU.
+ *   wav: [B, S] samples with leading dimension ldw, fp32 in (-1, 1) or (wav_is_i16) int16 PCM taken as value / 32768;
+ *   n_samples: int32 [B] clip lengths (clamped to S), NULL = every clip has S samples;
+ *   w: fp32 [C, 10] taps, gamma / beta: fp32 [C];
+ *   out: rows (b, t), row b*T_rows + t at out + row*ldo, C channels each - 16-bit, or fp32 with dtype = L2S_F32: the A operand
+ *   of the L2S_MODE_CONV1D tap-GEMM of layer 1.
+ * Each clip is normalised alone: clip b has L0 = (n_b - 10) / 5 + 1 frames (0 below 10 samples), the statistics of a channel
+ * are taken over those frames only (biased variance), rows L0 <= t < T_rows are written as zeros.  T_rows >= (S - 10) / 5 + 1.
+ * The statistics are accumulated in fp64 in a fixed order (no atomics): the same bits for a clip from run to run and whatever
+ * its batch mates.  workspace: l2s_wave_stem_workspace bytes of device memory (0 = bad shape).  Supported: C = 512; other
+ * widths return L2S_EUNSUPPORTED.  B <= 65535, S < 2^30.
+ */
+size_t l2s_wave_stem_workspace(int B, int C);
+int l2s_wave_stem(const void* wav, int wav_is_i16, int64_t ldw, const int32_t* n_samples, int B, int S, const float* w,
+                  const float* gamma, const float* beta, float eps, void* out, int ldo, int T_rows, int C, void* workspace,
+                  size_t workspace_bytes, int dtype, void* stream);
+/*
+ * l2s_kmeans_assign - nearest-centroid labels (avhubert/clustering/dump_km_label.py:26-52, ApplyKmeans.__call__: the argmin of
+ * |x|^2 - 2 x C + |c|^2, here without the row-constant |x|^2), csrc/kmeans.hip.  Everything fp32, products on the f32-input
+ * matrix instruction; the [M, K] distances are never written.
+ *   x: fp32 rows (b, t), row b*T + t at x + row*ldx, D features; centers: fp32 [K, D]; cnorm: fp32 [K] = |c_k|^2;
+ *   ids: int32 [B*T] = argmin_k (cnorm[k] - 2 x . c_k), the lowest index on a tie; -1 for rows t >= lens[b]*len_mul;
+ *   best2: NULL or fp32 [B*T, 2] = (smallest, second smallest) of cnorm[k] - 2 x . c_k (zeros for masked rows).
+ * Supported: D a multiple of 32 up to 1024, 2 <= K <= 1024; x and centers 16-byte aligned, ldx a multiple of 4.
+ */
+int l2s_kmeans_assign(const float* x, int ldx, const float* centers, const float* cnorm, const int32_t* lens, int len_mul, int B,
+                      int T, int D, int K, int32_t* ids, float* best2, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -110,6 +110,9 @@ SIGNATURES = {
     "l2s_mel_l1_sc": ([_vp, _i, _vp, _i, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp], _i),
     "l2s_ctc_loss_workspace": ([_i, _i, _i], ctypes.c_size_t),
     "l2s_ctc_loss": ([_vp, _i, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _i, _vp, ctypes.c_size_t, _vp, _vp], _i),
+    "l2s_wave_stem_workspace": ([_i, _i], ctypes.c_size_t),
+    "l2s_wave_stem": ([_vp, _i, ctypes.c_int64, _vp, _i, _i, _vp, _vp, _vp, _f, _vp, _i, _i, _i, _vp, ctypes.c_size_t, _i, _vp], _i),
+    "l2s_kmeans_assign": ([_vp, _i, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp], _i),
 }
 
 _lib = None

@@ -92,7 +92,8 @@ class _WeightNormConv1d(nn.Module):
 
 
 class TransformerEncoder(nn.Module):
-    """fairseq TransformerEncoder (called at hubert.py:739): pos_conv + N pre-LN layers + final layer_norm."""
+    """fairseq TransformerEncoder (called at hubert.py:739): pos_conv + N pre-LN layers + final layer_norm, or with
+    layer_norm_first=False (HuBERT-base, speech_units.py) pos_conv + layer_norm + N post-LN layers."""
 
     def __init__(self, cfg: AVHubertConfig, dtype=ops.F16):
         super().__init__()
@@ -105,10 +106,9 @@ class TransformerEncoder(nn.Module):
         self.layer_norm = nn.LayerNorm(d, eps=1e-5)
         self.dtype = dtype
         self._packed = None
-        if not cfg.layer_norm_first:
-            raise NotImplementedError("only layer_norm_first=True (AV-HuBERT large) is built")
 
-    def pack(self, dev):
+    def pack(self, dev, n_layers=None):
+        """Upload the packed weights; n_layers: only the first n_layers layers (an early exit never needs the rest)."""
         t16 = ops.torch_dtype(self.dtype)
         cfg = self.cfg
         d, G, k = cfg.encoder_embed_dim, cfg.conv_pos_groups, cfg.conv_pos
@@ -119,7 +119,7 @@ class TransformerEncoder(nn.Module):
         P = {"pc_w": w.view(G, cg, cg, k).permute(0, 1, 3, 2).reshape(G, cg, k * cg).to(dev, t16).contiguous(),
              "pc_b": pc.bias.detach().float().to(dev).contiguous(), "layers": []}
         scale = (d // cfg.encoder_attention_heads) ** -0.5
-        for L in self.layers:
+        for L in (self.layers if n_layers is None else self.layers[:n_layers]):
             a = L.self_attn
             wq = a.q_proj.weight.detach().float() * scale
             bq = a.q_proj.bias.detach().float() * scale
@@ -144,8 +144,13 @@ class TransformerEncoder(nn.Module):
                     self.layer_norm.bias.detach().float().to(dev).contiguous())
         self._packed = P
 
-    def forward_rows(self, x32, x16, lens, B, T):
-        """x32/x16: [B*T, d] fp32 / 16-bit copies of the input with padded rows already zeroed.  Returns fp32 [B*T, d]."""
+    def forward_rows(self, x32, x16, lens, B, T, output_layer=None):
+        """x32/x16: [B*T, d] fp32 / 16-bit copies of the input with padded rows already zeroed.  Returns fp32 [B*T, d].
+        output_layer (layer_norm_first=False only): the stream after that many layers, with no further norm."""
+        if not self.cfg.layer_norm_first:
+            return self._forward_rows_post_ln(x32, x16, lens, B, T, output_layer)
+        if output_layer is not None:
+            raise NotImplementedError("output_layer is built for layer_norm_first=False only")
         dev = x32.device
         if self._packed is None or self._packed["pc_b"].device != dev:
             self.pack(dev)
@@ -184,6 +189,49 @@ class TransformerEncoder(nn.Module):
             ops.residual_linear(f, e["w2"], e["b2"], x, M=M, N=d, K=F, dtype=dt, cache=e, key="w2",
                                 ln=(nxt[0], nxt[1], 1e-5, out if last else h))
         return out
+
+    def _forward_rows_post_ln(self, x32, x16, lens, B, T, output_layer):
+        """fairseq TransformerEncoder.extract_features / TransformerSentenceEncoderLayer.forward with layer_norm_first=False:
+        x = layer_norm(x + GELU(pos_conv(x))), then per layer x = LN1(x + attn(x)), x = LN2(x + fc2(GELU(fc1(x)))).
+        Every sum goes to the scratch stream s and the LayerNorm that follows writes the fp32 stream and the GEMM operand in one
+        launch (y / y2; never in place)."""
+        dev = x32.device
+        n = len(self.layers) if output_layer is None else int(output_layer)
+        if not 0 <= n <= len(self.layers):
+            raise ValueError(f"output_layer={output_layer}: the encoder has {len(self.layers)} layers")
+        P = self._packed
+        if P is None or P["pc_b"].device != dev or len(P["layers"]) < n:
+            self.pack(dev, n)
+            P = self._packed
+        dt, cfg = self.dtype, self.cfg
+        t16 = ops.torch_dtype(dt)
+        d, H, F = cfg.encoder_embed_dim, cfg.encoder_attention_heads, cfg.encoder_ffn_embed_dim
+        G, k = cfg.conv_pos_groups, cfg.conv_pos
+        cg = d // G
+        M = B * T
+        s = torch.empty(M, d, device=dev, dtype=torch.float32)
+        x = torch.empty(M, d, device=dev, dtype=torch.float32)
+        h = x if dt == ops.F32 else torch.empty(M, d, device=dev, dtype=t16)
+
+        def norm(ln):
+            ops.layernorm(s, ln[0], ln[1], 1e-5, x, M=M, C=d, y2=None if h is x else h, ldy2=0 if h is x else d, dtype=dt)
+
+        ops.tapgemm(x16, P["pc_w"], s, M=M, N=cg, Cin=cg, ntaps=k, lda=d, ldc=d, mode=MODE_CONV1D, T_out=T, T_in=T,
+                    stride=1, dil=1, off=-(k // 2), bias=P["pc_b"], act=ACT_GELU, R=x32, ldr=d, flags=F_RES_POST,
+                    dtype=dt, groups=G, a_gstride=cg, c_gstride=cg, w_gstride=cg * k * cg)
+        norm(P["lnf"])
+        qkv = torch.empty(M, 3 * d, device=dev, dtype=t16)
+        att = torch.empty(M, d, device=dev, dtype=t16)
+        f = torch.empty(M, F, device=dev, dtype=t16)
+        for e in P["layers"][:n]:
+            ops.tapgemm(h, e["wqkv"], qkv, M=M, N=3 * d, Cin=d, bias=e["bqkv"], dtype=dt)
+            ops.attention(qkv, att, B=B, T=T, H=H, lens=lens, len_mul=1, dtype=dt)
+            ops.tapgemm(att, e["wo"], s, M=M, N=d, Cin=d, bias=e["bo"], R=x, ldr=d, flags=F_RES_POST, dtype=dt)
+            norm(e["ln1"])
+            ops.tapgemm(h, e["w1"], f, M=M, N=F, Cin=d, bias=e["b1"], act=ACT_GELU, dtype=dt)
+            ops.tapgemm(f, e["w2"], s, M=M, N=d, Cin=F, bias=e["b2"], R=x, ldr=d, flags=F_RES_POST, dtype=dt)
+            norm(e["ln2"])
+        return x
 
 
 class SubModel(nn.Module):

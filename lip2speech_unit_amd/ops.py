@@ -622,6 +622,66 @@ def ctc_loss(logits, targets, tgt_lens, tgt_offs, workspace, nll, *, B, L, V, S_
         nbytes=4.0 * B * L * V)
 
 
+def wave_stem_frames(n):
+    """Frames of HuBERT's first conv layer (k = 10, stride 5, no padding) for n samples."""
+    return (n - 10) // 5 + 1 if n >= 10 else 0
+
+
+def wave_stem_workspace_bytes(B, C):
+    n = _lib.load().l2s_wave_stem_workspace(B, C)
+    if n == 0:
+        raise L2SError(f"l2s_wave_stem_workspace: bad shape (B={B}, C={C})")
+    return n
+
+
+def wave_stem(wav, w, gamma, beta, workspace, out, *, B, S, T_rows, C=512, n_samples=None, ldw=None, ldo=None, eps=1e-5, dtype=F16):
+    """HuBERT's waveform stem in one call (csrc/wavestem.hip): Conv1d(1 -> C, 10, stride 5), GroupNorm(C, C) over each clip's own
+    frames, GELU.  wav fp32 or int16 [B, S]; w fp32 [C, 10]; out [B*T_rows, C] of `dtype` (rows past a clip's frames are
+    zeros); workspace: wave_stem_workspace_bytes(B, C) bytes."""
+    if wav.dtype not in (torch.float32, torch.int16):
+        raise L2SError(f"wav: expected float32 or int16, got {wav.dtype}")
+    if n_samples is not None and n_samples.dtype != torch.int32:
+        raise L2SError("n_samples must be int32")
+    _req(wav, None, "wav"), _req(w, torch.float32, "w"), _req(gamma, torch.float32, "gamma"), _req(beta, torch.float32, "beta")
+    _req(out, _TORCH16[dtype], "out")
+    ldw = ldw if ldw is not None else S
+    ldo = ldo if ldo is not None else C
+    if w.numel() < C * 10 or not w.is_contiguous() or gamma.numel() < C or beta.numel() < C:
+        raise L2SError("wave_stem: w [C, 10], gamma / beta [C]")
+    if (B - 1) * ldw + S > _extent(wav) or (n_samples is not None and n_samples.numel() < B):
+        raise L2SError("wave_stem: wav smaller than [B, S] of ldw / n_samples shorter than B")
+    if (B * T_rows - 1) * ldo + C > _extent(out):
+        raise L2SError("wave_stem: out smaller than B*T_rows rows of ldo")
+    rows = float(B) * T_rows
+    _run("l2s_wave_stem", lambda: _lib.load().l2s_wave_stem(
+        _ptr(wav), int(wav.dtype == torch.int16), ldw, _ptr(n_samples), B, S, _ptr(w), _ptr(gamma), _ptr(beta), float(eps), _ptr(out),
+        ldo, T_rows, C, _ptr(workspace), workspace.numel() * workspace.element_size(), dtype, _stream()),
+        flops=2.0 * rows * C * 10, nbytes=3.0 * B * S * wav.element_size() + rows * C * out.element_size())
+
+
+def kmeans_assign(x, centers, cnorm, ids, *, B, T, D, K, ldx=None, lens=None, len_mul=1, best2=None):
+    """Nearest-centroid labels in one launch (csrc/kmeans.hip): ids int32 [B*T] = argmin_k (cnorm[k] - 2 x . centers[k]) over
+    fp32 rows x [B*T, ldx], lowest index on ties, -1 past lens[b]*len_mul; best2 (optional) fp32 [B*T, 2] = the two smallest."""
+    _req(x, torch.float32, "x"), _req(centers, torch.float32, "centers"), _req(cnorm, torch.float32, "cnorm")
+    _req(ids, torch.int32, "ids")
+    if lens is not None:
+        _req(lens, torch.int32, "lens")
+    if best2 is not None:
+        _req(best2, torch.float32, "best2")
+    ldx = ldx if ldx is not None else D
+    if (B * T - 1) * ldx + D > _extent(x):
+        raise L2SError("kmeans_assign: x smaller than B*T rows of ldx")
+    if not centers.is_contiguous() or centers.numel() < K * D or cnorm.numel() < K:
+        raise L2SError("kmeans_assign: centers [K, D] dense, cnorm [K]")
+    if ids.numel() < B * T or not ids.is_contiguous() or (lens is not None and lens.numel() < B):
+        raise L2SError("kmeans_assign: ids shorter than B*T / lens shorter than B")
+    if best2 is not None and (best2.numel() < 2 * B * T or not best2.is_contiguous()):
+        raise L2SError("kmeans_assign: best2 [B*T, 2] dense")
+    _run("l2s_kmeans_assign", lambda: _lib.load().l2s_kmeans_assign(
+        _ptr(x), ldx, _ptr(centers), _ptr(cnorm), _ptr(lens), len_mul, B, T, D, K, _ptr(ids), _ptr(best2), _stream()),
+        flops=2.0 * B * T * K * D, nbytes=4.0 * B * T * D + 4.0 * K * D + 4.0 * B * T)
+
+
 # ---- torch.library registration ("PyTorch-ROCm custom ops", SURVEY 8b last row) --------------------------------------------------
 # Every launcher above is ALSO a dispatcher-visible operator `torch.ops.lip2speech.<name>` (schema below, CUDA = HIP kernel only: a
 # CPU tensor finds no kernel and raises; a fake / meta implementation gives shapes to torch.compile and fake-tensor tracing), and
@@ -712,13 +772,17 @@ _SCHEMAS = {
                  "int Tm_targ, int crop_len, Tensor? lens=None, int len_mul=4, int n_mels=80) -> ()",
     "ctc_loss": "(Tensor logits, Tensor targets, Tensor tgt_lens, Tensor tgt_offs, Tensor(a!) workspace, Tensor(b!) nll, *, int B, "
                 "int L, int V, int S_max, int blank=0, int? ldl=None, Tensor? lens=None, int len_mul=2) -> ()",
+    "wave_stem": "(Tensor wav, Tensor w, Tensor gamma, Tensor beta, Tensor(a!) workspace, Tensor(b!) out, *, int B, int S, int T_rows, "
+                 "int C=512, Tensor? n_samples=None, int? ldw=None, int? ldo=None, float eps=1e-05, int dtype=0) -> ()",
+    "kmeans_assign": "(Tensor x, Tensor centers, Tensor cnorm, Tensor(a!) ids, *, int B, int T, int D, int K, int? ldx=None, "
+                     "Tensor? lens=None, int len_mul=1, Tensor(b!)? best2=None) -> ()",
 }
 # C-ABI entry each operator launches (tests/test_torchlib_cpu.py: every device entry of include/lip2speech_hip.h has a twin)
 ENTRY_OF = {n: "l2s_" + n for n in _SCHEMAS}
 ENTRY_OF.update({"maxpool2d_3x3s2": "l2s_maxpool2d_3x3s2", "avgpool_hw": "l2s_avgpool_hw"})
 # host-side queries of the ABI (no launch, nothing for the dispatcher to see)
 HOST_QUERIES = ("l2s_abi_version", "l2s_build_info", "l2s_tapgemm_variant", "l2s_tapgemm_epilogue_family", "l2s_beam_decode_workspace",
-                "l2s_ctc_beam_workspace", "l2s_ctc_loss_workspace")
+                "l2s_ctc_beam_workspace", "l2s_ctc_loss_workspace", "l2s_wave_stem_workspace")
 # SURVEY 8(b)'s operator names -> the entry that implements them (`mel_head` is a composition of linear_epilogue launches,
 # conformer.py::Conformer.forward_rows; it has no kernel of its own)
 ALIASES = {"frontend3d_stem": "stem_pool_fused", "resnet_trunk": "basiclayer_fused", "linear_epilogue": "tapgemm",

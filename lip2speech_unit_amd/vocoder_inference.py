@@ -3,7 +3,10 @@
 
   python -m lip2speech_unit_amd.vocoder_inference <config.json> <label/test.tsv> <dict.unt.txt> \
       --output_dir D --checkpoint_file C -n -1 [--pad N] [--synthetic_weights] [--mel_from_audio]
+      [--units_from_audio --hubert <ckpt> --kmeans <km.bin|centers.npy> [--units_layer 6] [--units_dtype f32|f16|bf16]]
 --mel_from_audio: the mel conditioning is analysed from audio/*.wav on the device (audio.TacotronSTFT); mel/ is not read.
+--units_from_audio: the units are computed from audio/*.wav on the device (speech_units.SpeechUnitExtractor); the .unt file is
+not read.  With both flags stage 2 runs from a folder of wavs and speaker embeddings alone.
 Writes D/pred_wav/<spk>/<utt>.wav (int16, 16 kHz) like :157-165.
 """
 import argparse
@@ -20,6 +23,18 @@ from .data import MelCodeDataset, parse_manifest
 from .vocoder import AttrDict, MelCodeGenerator
 
 
+def manifest_from_audio(manifest_path, extractor, batch=16):
+    """parse_manifest's (audio_files, mel_files, codes) with the codes computed from the wavs instead of read from <manifest>.unt."""
+    from . import audio
+    from .extract_units import extract
+    with open(manifest_path) as f:
+        root = f.readline().strip()
+        audio_files = [os.path.join(root, line.strip().split("\t")[2]) for line in f if line.strip()]
+    units = extract(extractor, [audio.read_wav_s16(pth) for pth in audio_files], batch)
+    mels = [pth.replace("/audio/", "/mel/")[:-4] + ".npy" for pth in audio_files]
+    return audio_files, mels, [" ".join(str(int(v)) for v in ids) for ids in units]
+
+
 def main(argv=None):
     p = argparse.ArgumentParser()
     p.add_argument("config_file")
@@ -34,7 +49,14 @@ def main(argv=None):
     p.add_argument("--synthetic_weights", action="store_true")
     p.add_argument("--dtype", default="f16", choices=["f16", "bf16"])
     p.add_argument("--mel_from_audio", action="store_true")
+    p.add_argument("--units_from_audio", action="store_true")
+    p.add_argument("--hubert", default=None)
+    p.add_argument("--kmeans", default=None)
+    p.add_argument("--units_layer", type=int, default=6)
+    p.add_argument("--units_dtype", default="f32", choices=["f32", "f16", "bf16"])
     a = p.parse_args(argv)
+    if a.units_from_audio and not (a.hubert and a.kmeans):
+        p.error("--units_from_audio needs --hubert and --kmeans")
     if a.code_file is not None:
         raise NotImplementedError("--code_file (units without mel/speaker) is not the multi-input path")
     if not torch.cuda.is_available():
@@ -50,7 +72,16 @@ def main(argv=None):
         gen.load_state_dict(torch.load(a.checkpoint_file, map_location="cpu")["generator"])   # :119-120
     gen.cuda().eval()
     gen.remove_weight_norm()                                                                   # :142-143
-    ds = MelCodeDataset(parse_manifest(a.input_code_file), h.code_hop_size, h.mel_hop_size, code_dict_path=a.code_dict_path,
+    if a.units_from_audio:
+        from . import speech_units
+        from .extract_units import DTYPES
+        udt = DTYPES[a.units_dtype]
+        extractor = speech_units.SpeechUnitExtractor(speech_units.load_hubert(a.hubert, dtype=udt), speech_units.load_kmeans(a.kmeans),
+                                                     layer=a.units_layer, dtype=udt)
+        file_list = manifest_from_audio(a.input_code_file, extractor)
+    else:
+        file_list = parse_manifest(a.input_code_file)
+    ds = MelCodeDataset(file_list, h.code_hop_size, h.mel_hop_size, code_dict_path=a.code_dict_path,
                         pad=a.pad, mel_from_audio=a.mel_from_audio)
     os.makedirs(a.output_dir, exist_ok=True)
     n = len(ds) if a.n == -1 else min(a.n, len(ds))
