@@ -538,6 +538,49 @@ int l2s_wave_stem(const void* wav, int wav_is_i16, int64_t ldw, const int32_t* n
 int l2s_kmeans_assign(const float* x, int ldx, const float* centers, const float* cnorm, const int32_t* lens, int len_mul, int B,
                       int T, int D, int K, int32_t* ids, float* best2, void* stream);
 
+/*
+ * Mini-batch k-means fit: what avhubert/clustering/learn_kmeans.py:25-47 (estimator arguments) and :88-121 (fit, score) ask of
+ * scikit-learn's MiniBatchKMeans, csrc/kmeans_fit.hip; the host loop is lip2speech_unit_amd/kmeans_fit.py.  Everything fp32 in
+ * memory; every sum is taken in a fixed order without floating-point atomics, so results are bit-identical from run to run.
+ * Common to the four entries: x is fp32 [N, ldx] (16-byte aligned, ldx a multiple of 4, ldx >= D); a batch or subset of it is named
+ * by `rows`, int32 positions into x (repeats are legal; an index outside [0, N) is read as the nearest valid row), or is the first
+ * M rows when rows = NULL.  Supported: D a multiple of 32 up to 1024, 2 <= K <= 1024, N < 2^31 with rows.
+ *
+ * l2s_kmeans_nearest - one mini-batch assignment (the labels and inertia of a step, learn_kmeans.py:116, and of the score, :119):
+ *   ids: NULL or int32 [M] = argmin_k |x - c_k|^2, the lowest index on a tie (the distance tile of l2s_kmeans_assign);
+ *   dmin: NULL or fp32 [M] = max(0, |x|^2 + cnorm[k] - 2 x . c_k) at that k; inertia: NULL or one double = sum of dmin
+ *   (32-row partials, then one finishing block).  workspace: l2s_kmeans_nearest_workspace(M) bytes, needed with inertia.
+ *   M < 2^31 - 32.  The [M, K] distances are never written.
+ * l2s_kmeans_update - the centre update of a step: for every centre with n > 0 members in the batch (ids[i] = k)
+ *   c_k <- (c_k w_k + sum of its rows) / (w_k + n), w_k <- w_k + n; other centres and counts are copied.  Members are summed in
+ *   ascending batch position.  centers_out / counts_out may be centers / counts themselves.  cnorm_out: fp32 [K] = |c_k|^2 of the
+ *   new centres (summed in fp64).  Labels outside [0, K) belong to no centre.  workspace: l2s_kmeans_update_workspace(M, K)
+ *   bytes (0 = unsupported).  M <= 2^24; counts are exact up to 2^24 samples per centre.
+ * l2s_kmeans_pp_pot - greedy k-means++: cand int32 [t <= 16] are positions in the subset (0 .. m - 1); closest: fp32 [m] or NULL
+ *   (= +inf).  Without closest_out: pot[j] = sum_i min(closest[i], |x_i - x_cand[j]|^2), doubles [t].  With closest_out (fp32 [m],
+ *   may be closest itself): one candidate - cand[0] when t = 1 and select = NULL, or cand[argmin select[0..t)] (doubles, the
+ *   first of equal ones) - gets closest_out[i] = min(closest[i], |x_i - x_cand|^2); pot (if given) [1] = their sum, chosen (if
+ *   given, with select) [1] = that candidate's position.  The squared distance is the direct fp32 sum of (x - c)^2: exact on
+ *   small integers.  workspace: l2s_kmeans_pp_workspace(m) bytes.  m < 2^31 - 64.
+ * l2s_kmeans_pp_pick - searchsorted(cumsum(closest), thresholds, side = "left") clipped to m - 1, one block, prefix sums in
+ *   fp64: threshold j = u[j] * (scale ? *scale : 1) (u, scale: doubles on the device), idx: int32 [t <= 16], total: NULL or one
+ *   double = the sum of closest.  m <= 2^24.
+ */
+size_t l2s_kmeans_nearest_workspace(int M);
+int l2s_kmeans_nearest(const float* x, int ldx, int64_t N, const int32_t* rows, int M, const float* centers, const float* cnorm,
+                       int D, int K, int32_t* ids, float* dmin, double* inertia, void* workspace, size_t workspace_bytes,
+                       void* stream);
+size_t l2s_kmeans_update_workspace(int M, int K);
+int l2s_kmeans_update(const float* x, int ldx, int64_t N, const int32_t* rows, int M, const int32_t* ids, const float* centers,
+                      const float* counts, int D, int K, float* centers_out, float* counts_out, float* cnorm_out, void* workspace,
+                      size_t workspace_bytes, void* stream);
+size_t l2s_kmeans_pp_workspace(int m);
+int l2s_kmeans_pp_pot(const float* x, int ldx, int64_t N, const int32_t* rows, int m, int D, const int32_t* cand, int t,
+                      const float* closest, const double* select, double* pot, float* closest_out, int32_t* chosen,
+                      void* workspace, size_t workspace_bytes, void* stream);
+int l2s_kmeans_pp_pick(const float* closest, int m, const double* u, int t, const double* scale, int32_t* idx, double* total,
+                       void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -113,6 +113,13 @@ SIGNATURES = {
     "l2s_wave_stem_workspace": ([_i, _i], ctypes.c_size_t),
     "l2s_wave_stem": ([_vp, _i, ctypes.c_int64, _vp, _i, _i, _vp, _vp, _vp, _f, _vp, _i, _i, _i, _vp, ctypes.c_size_t, _i, _vp], _i),
     "l2s_kmeans_assign": ([_vp, _i, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp], _i),
+    "l2s_kmeans_nearest_workspace": ([_i], ctypes.c_size_t),
+    "l2s_kmeans_nearest": ([_vp, _i, ctypes.c_int64, _vp, _i, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, ctypes.c_size_t, _vp], _i),
+    "l2s_kmeans_update_workspace": ([_i, _i], ctypes.c_size_t),
+    "l2s_kmeans_update": ([_vp, _i, ctypes.c_int64, _vp, _i, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, ctypes.c_size_t, _vp], _i),
+    "l2s_kmeans_pp_workspace": ([_i], ctypes.c_size_t),
+    "l2s_kmeans_pp_pot": ([_vp, _i, ctypes.c_int64, _vp, _i, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, ctypes.c_size_t, _vp], _i),
+    "l2s_kmeans_pp_pick": ([_vp, _i, _vp, _i, _vp, _vp, _vp, _vp], _i),
 }
 
 _lib = None

@@ -15,104 +15,25 @@
 // reads are bank-conflict free).  22.5 KB of LDS.  Centres past K are computed on centre K - 1 and discarded.
 // Traffic: x once per pass (K = 200: twice, from L2), the centres once per block (K D 4 bytes = 614 KB at 200 x 768, L2
 // resident), 4 (+8) bytes per row out.
-#include "l2s_common.h"
-#include <math.h>
+#include "kmeans_tile.h"
 
 namespace {
 
-typedef __attribute__((ext_vector_type(16))) float f32x16_t;
-
-constexpr int BM = 32, BN = 128, BK = 32;
-constexpr int LDX = BM + 4, LDC = BN + 4;
-
-struct Best {
-  float d, d2;
-  int i;
-};
-
-// a, b: disjoint candidate sets; ties between equal distances go to the lower index
-__device__ __forceinline__ Best merge(const Best a, const Best b) {
-  Best r;
-  if (b.d < a.d || (b.d == a.d && b.i < a.i)) {
-    r.d = b.d; r.i = b.i; r.d2 = fminf(a.d, b.d2);
-  } else {
-    r.d = a.d; r.i = a.i; r.d2 = fminf(a.d2, b.d);
-  }
-  return r;
-}
+using namespace kmeans_tile;   // the tile itself: kmeans_tile.h (shared with l2s_kmeans_nearest, kmeans_fit.hip)
 
 __global__ __launch_bounds__(256) void kmeans_assign_kernel(const float* __restrict__ x, const int ldx, const float* __restrict__ cen,
                                                             const float* __restrict__ cnorm, const int32_t* __restrict__ lens,
                                                             const int len_mul, const int M, const int T, const int D, const int K,
                                                             int32_t* __restrict__ ids, float* __restrict__ best2) {
-  __shared__ float sX[BK][LDX];
-  __shared__ float sC[BK][LDC];
-  __shared__ Best sBest[4][BM];
-  const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  __shared__ Smem sm;
+  const int tid = threadIdx.x;
   const int m0 = blockIdx.x * BM;
-  const int lr = lane & 31, lh = lane >> 5;
-
-  // fetch roles: x chunk = 32 rows x 8 float4 (one per thread); centre chunk = 128 rows x 8 float4 (four per thread)
-  const int xr = tid >> 3, xk = (tid & 7) * 4;
-  const float* xrow = x + (int64_t)min(m0 + xr, M - 1) * ldx + xk;
-
-  Best best;
-  best.d = INFINITY; best.d2 = INFINITY; best.i = 0x7fffffff;
-
-  for (int n0 = 0; n0 < K; n0 += BN) {
-    const int nw = n0 + 32 * wave;
-    const bool wave_on = nw < K;                         // wave-uniform
-    f32x16_t acc;
-#pragma unroll
-    for (int e = 0; e < 16; ++e) acc[e] = 0.f;
-    for (int d0 = 0; d0 < D; d0 += BK) {
-      const float4 vx = *reinterpret_cast<const float4*>(xrow + d0);
-      float4 vc[4];
-#pragma unroll
-      for (int h = 0; h < 4; ++h) {
-        const int n = min(n0 + xr + 32 * h, K - 1);
-        vc[h] = *reinterpret_cast<const float4*>(cen + (int64_t)n * D + d0 + xk);
-      }
-      __syncthreads();                                   // the previous chunk's fragments are read
-      sX[xk + 0][xr] = vx.x; sX[xk + 1][xr] = vx.y; sX[xk + 2][xr] = vx.z; sX[xk + 3][xr] = vx.w;
-#pragma unroll
-      for (int h = 0; h < 4; ++h) {
-        const int r = xr + 32 * h;
-        sC[xk + 0][r] = vc[h].x; sC[xk + 1][r] = vc[h].y; sC[xk + 2][r] = vc[h].z; sC[xk + 3][r] = vc[h].w;
-      }
-      __syncthreads();
-      if (wave_on) {
-#pragma unroll
-        for (int s = 0; s < BK / 2; ++s) {
-          const int k = 2 * s + lh;
-          acc = __builtin_amdgcn_mfma_f32_32x32x2f32(sC[k][32 * wave + lr], sX[k][lr], acc, 0, 0, 0);
-        }
-      }
-    }
-    if (wave_on) {
-      // register e of a lane: centre nw + 8 (e >> 2) + 4 lh + (e & 3) (ascending in e), row m0 + lr
-#pragma unroll
-      for (int e = 0; e < 16; ++e) {
-        const int n = nw + 8 * (e >> 2) + 4 * lh + (e & 3);
-        if (n < K) {
-          const float dist = fmaf(-2.0f, acc[e], cnorm[n]);
-          if (dist < best.d) { best.d2 = best.d; best.d = dist; best.i = n; }
-          else best.d2 = fminf(best.d2, dist);
-        }
-      }
-    }
-  }
-  {
-    Best o;
-    o.d = __shfl_xor(best.d, 32, 64); o.d2 = __shfl_xor(best.d2, 32, 64); o.i = __shfl_xor(best.i, 32, 64);
-    best = merge(best, o);
-  }
-  if (lh == 0) sBest[wave][lr] = best;
-  __syncthreads();
+  const float* xrow = x + (int64_t)min(m0 + (tid >> 3), M - 1) * ldx + (tid & 7) * 4;
+  float unused;
+  const Best r = scan_centres<false>(xrow, cen, cnorm, D, K, sm, unused);
   if (tid < BM) {
     const int m = m0 + tid;
     if (m < M) {
-      Best r = merge(merge(sBest[0][tid], sBest[1][tid]), merge(sBest[2][tid], sBest[3][tid]));
       bool keep = true;
       if (lens) {
         const int clip = m / T;

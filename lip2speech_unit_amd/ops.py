@@ -682,6 +682,125 @@ def kmeans_assign(x, centers, cnorm, ids, *, B, T, D, K, ldx=None, lens=None, le
         flops=2.0 * B * T * K * D, nbytes=4.0 * B * T * D + 4.0 * K * D + 4.0 * B * T)
 
 
+def _ws_bytes(t):
+    return t.numel() * t.element_size()
+
+
+def _km_batch(name, x, rows, M, D, ldx):
+    """Shared checks of the k-means fit entries' batch arguments; returns (ldx, N)."""
+    _req(x, torch.float32, "x")
+    if x.dim() != 2:
+        raise L2SError(f"{name}: x [N, ldx]")
+    ldx = ldx if ldx is not None else (x.stride(0) if x.shape[0] > 1 else max(x.shape[1], D))
+    N = x.shape[0]
+    if x.shape[1] < D or (N - 1) * ldx + D > _extent(x):
+        raise L2SError(f"{name}: x smaller than N rows of ldx")
+    if rows is not None:
+        _req(rows, torch.int32, "rows")
+        if rows.numel() < M or not rows.is_contiguous():
+            raise L2SError(f"{name}: rows shorter than M")
+    elif N < M:
+        raise L2SError(f"{name}: x has fewer than M rows")
+    return ldx, N
+
+
+def kmeans_nearest_workspace_bytes(M):
+    n = _lib.load().l2s_kmeans_nearest_workspace(M)
+    if n == 0:
+        raise L2SError(f"l2s_kmeans_nearest_workspace: unsupported size (M={M})")
+    return n
+
+
+def kmeans_update_workspace_bytes(M, K):
+    n = _lib.load().l2s_kmeans_update_workspace(M, K)
+    if n == 0:
+        raise L2SError(f"l2s_kmeans_update_workspace: unsupported size (M={M}, K={K}; M <= 2^24, 2 <= K <= 1024)")
+    return n
+
+
+def kmeans_pp_workspace_bytes(m):
+    n = _lib.load().l2s_kmeans_pp_workspace(m)
+    if n == 0:
+        raise L2SError(f"l2s_kmeans_pp_workspace: unsupported size (m={m})")
+    return n
+
+
+def kmeans_nearest(x, centers, cnorm, *, M, D, K, rows=None, ids=None, dmin=None, inertia=None, workspace=None, ldx=None):
+    """One mini-batch assignment (csrc/kmeans_fit.hip): over the batch x[rows] (or x[:M]) ids int32 [M] = the nearest centre
+    (lowest index on a tie), dmin fp32 [M] = max(0, |x|^2 + cnorm - 2 x.c) there, inertia float64 [1] = their sum in a fixed
+    order.  workspace: kmeans_nearest_workspace_bytes(M) bytes, needed with inertia."""
+    ldx, N = _km_batch("kmeans_nearest", x, rows, M, D, ldx)
+    _req(centers, torch.float32, "centers"), _req(cnorm, torch.float32, "cnorm")
+    if not centers.is_contiguous() or centers.numel() < K * D or cnorm.numel() < K:
+        raise L2SError("kmeans_nearest: centers [K, D] dense, cnorm [K]")
+    for t, dt, nm, n in ((ids, torch.int32, "ids", M), (dmin, torch.float32, "dmin", M), (inertia, torch.float64, "inertia", 1)):
+        if t is not None:
+            _req(t, dt, nm)
+            if t.numel() < n or not t.is_contiguous():
+                raise L2SError(f"kmeans_nearest: {nm} shorter than {n}")
+    if workspace is not None:
+        _req(workspace, None, "workspace")
+    _run("l2s_kmeans_nearest", lambda: _lib.load().l2s_kmeans_nearest(
+        _ptr(x), ldx, N, _ptr(rows), M, _ptr(centers), _ptr(cnorm), D, K, _ptr(ids), _ptr(dmin), _ptr(inertia), _ptr(workspace),
+        _ws_bytes(workspace) if workspace is not None else 0, _stream()),
+        flops=2.0 * M * K * D, nbytes=4.0 * M * D + 4.0 * K * D + 8.0 * M)
+
+
+def kmeans_update(x, ids, centers, counts, centers_out, counts_out, cnorm_out, workspace, *, M, D, K, rows=None, ldx=None):
+    """The centre update of a mini-batch step (csrc/kmeans_fit.hip): c <- (c w + sum of the batch rows labelled k) / (w + n),
+    w <- w + n for every centre with members, the others copied; cnorm_out = |c|^2 of the result.  centers_out / counts_out may
+    be centers / counts.  workspace: kmeans_update_workspace_bytes(M, K) bytes."""
+    ldx, N = _km_batch("kmeans_update", x, rows, M, D, ldx)
+    _req(ids, torch.int32, "ids"), _req(workspace, None, "workspace")
+    for t, nm, n in ((centers, "centers", K * D), (counts, "counts", K), (centers_out, "centers_out", K * D), (counts_out, "counts_out", K),
+                     (cnorm_out, "cnorm_out", K)):
+        _req(t, torch.float32, nm)
+        if t.numel() < n or not t.is_contiguous():
+            raise L2SError(f"kmeans_update: {nm} dense with {n} elements")
+    if ids.numel() < M or not ids.is_contiguous():
+        raise L2SError("kmeans_update: ids shorter than M")
+    _run("l2s_kmeans_update", lambda: _lib.load().l2s_kmeans_update(
+        _ptr(x), ldx, N, _ptr(rows), M, _ptr(ids), _ptr(centers), _ptr(counts), D, K, _ptr(centers_out), _ptr(counts_out),
+        _ptr(cnorm_out), _ptr(workspace), _ws_bytes(workspace), _stream()), flops=1.0 * M * D, nbytes=4.0 * M * D + 8.0 * K * D + 8.0 * M)
+
+
+def kmeans_pp_pot(x, cand, workspace, *, m, D, t, rows=None, closest=None, select=None, pot=None, closest_out=None, chosen=None,
+                  ldx=None):
+    """k-means++ potentials (csrc/kmeans_fit.hip): cand int32 [t <= 16] positions in the subset x[rows] (or x[:m]).  Without
+    closest_out: pot float64 [t] = sum_i min(closest[i], |x_i - x_cand|^2) (closest = None: +inf).  With closest_out: the new
+    closest of cand[0] (t = 1) or of cand[argmin select] - then chosen int32 [1] = its position - and pot [1] = its sum.
+    workspace: kmeans_pp_workspace_bytes(m) bytes."""
+    ldx, N = _km_batch("kmeans_pp_pot", x, rows, m, D, ldx)
+    _req(cand, torch.int32, "cand"), _req(workspace, None, "workspace")
+    n_pot = 1 if closest_out is not None else t
+    for a, dt, nm, n in ((closest, torch.float32, "closest", m), (select, torch.float64, "select", t), (pot, torch.float64, "pot", n_pot),
+                         (closest_out, torch.float32, "closest_out", m), (chosen, torch.int32, "chosen", 1)):
+        if a is not None:
+            _req(a, dt, nm)
+            if a.numel() < n or not a.is_contiguous():
+                raise L2SError(f"kmeans_pp_pot: {nm} shorter than {n}")
+    if cand.numel() < t or not cand.is_contiguous():
+        raise L2SError("kmeans_pp_pot: cand shorter than t")
+    _run("l2s_kmeans_pp_pot", lambda: _lib.load().l2s_kmeans_pp_pot(
+        _ptr(x), ldx, N, _ptr(rows), m, D, _ptr(cand), t, _ptr(closest), _ptr(select), _ptr(pot), _ptr(closest_out), _ptr(chosen),
+        _ptr(workspace), _ws_bytes(workspace), _stream()), flops=3.0 * m * D * n_pot, nbytes=4.0 * m * D + 8.0 * m)
+
+
+def kmeans_pp_pick(closest, u, idx, *, m, t, scale=None, total=None):
+    """searchsorted(cumsum(closest[:m]) in float64, u * scale, side="left") clipped to m - 1 (csrc/kmeans_fit.hip): u float64 [t <= 16]
+    and scale float64 [1] (None: 1) on the device, idx int32 [t], total float64 [1] = the sum of closest."""
+    _req(closest, torch.float32, "closest"), _req(u, torch.float64, "u"), _req(idx, torch.int32, "idx")
+    for a, nm in ((scale, "scale"), (total, "total")):
+        if a is not None:
+            _req(a, torch.float64, nm)
+            if a.numel() < 1:
+                raise L2SError(f"kmeans_pp_pick: {nm} is empty")
+    if closest.numel() < m or not closest.is_contiguous() or u.numel() < t or idx.numel() < t:
+        raise L2SError("kmeans_pp_pick: closest shorter than m / u, idx shorter than t")
+    _run("l2s_kmeans_pp_pick", lambda: _lib.load().l2s_kmeans_pp_pick(
+        _ptr(closest), m, _ptr(u) if t else None, t, _ptr(scale), _ptr(idx), _ptr(total), _stream()), nbytes=4.0 * m * (1 + t))
+
+
 # ---- torch.library registration ("PyTorch-ROCm custom ops", SURVEY 8b last row) --------------------------------------------------
 # Every launcher above is ALSO a dispatcher-visible operator `torch.ops.lip2speech.<name>` (schema below, CUDA = HIP kernel only: a
 # CPU tensor finds no kernel and raises; a fake / meta implementation gives shapes to torch.compile and fake-tensor tracing), and
@@ -776,13 +895,22 @@ _SCHEMAS = {
                  "int C=512, Tensor? n_samples=None, int? ldw=None, int? ldo=None, float eps=1e-05, int dtype=0) -> ()",
     "kmeans_assign": "(Tensor x, Tensor centers, Tensor cnorm, Tensor(a!) ids, *, int B, int T, int D, int K, int? ldx=None, "
                      "Tensor? lens=None, int len_mul=1, Tensor(b!)? best2=None) -> ()",
+    "kmeans_nearest": "(Tensor x, Tensor centers, Tensor cnorm, *, int M, int D, int K, Tensor? rows=None, Tensor(a!)? ids=None, "
+                      "Tensor(b!)? dmin=None, Tensor(c!)? inertia=None, Tensor(d!)? workspace=None, int? ldx=None) -> ()",
+    "kmeans_update": "(Tensor x, Tensor ids, Tensor centers, Tensor counts, Tensor(a!) centers_out, Tensor(b!) counts_out, "
+                     "Tensor(c!) cnorm_out, Tensor(d!) workspace, *, int M, int D, int K, Tensor? rows=None, int? ldx=None) -> ()",
+    "kmeans_pp_pot": "(Tensor x, Tensor cand, Tensor(a!) workspace, *, int m, int D, int t, Tensor? rows=None, Tensor? closest=None, "
+                     "Tensor? select=None, Tensor(b!)? pot=None, Tensor(c!)? closest_out=None, Tensor(d!)? chosen=None, "
+                     "int? ldx=None) -> ()",
+    "kmeans_pp_pick": "(Tensor closest, Tensor u, Tensor(a!) idx, *, int m, int t, Tensor? scale=None, Tensor(b!)? total=None) -> ()",
 }
 # C-ABI entry each operator launches (tests/test_torchlib_cpu.py: every device entry of include/lip2speech_hip.h has a twin)
 ENTRY_OF = {n: "l2s_" + n for n in _SCHEMAS}
 ENTRY_OF.update({"maxpool2d_3x3s2": "l2s_maxpool2d_3x3s2", "avgpool_hw": "l2s_avgpool_hw"})
 # host-side queries of the ABI (no launch, nothing for the dispatcher to see)
 HOST_QUERIES = ("l2s_abi_version", "l2s_build_info", "l2s_tapgemm_variant", "l2s_tapgemm_epilogue_family", "l2s_beam_decode_workspace",
-                "l2s_ctc_beam_workspace", "l2s_ctc_loss_workspace", "l2s_wave_stem_workspace")
+                "l2s_ctc_beam_workspace", "l2s_ctc_loss_workspace", "l2s_wave_stem_workspace", "l2s_kmeans_nearest_workspace",
+                "l2s_kmeans_update_workspace", "l2s_kmeans_pp_workspace")
 # SURVEY 8(b)'s operator names -> the entry that implements them (`mel_head` is a composition of linear_epilogue launches,
 # conformer.py::Conformer.forward_rows; it has no kernel of its own)
 ALIASES = {"frontend3d_stem": "stem_pool_fused", "resnet_trunk": "basiclayer_fused", "linear_epilogue": "tapgemm",
