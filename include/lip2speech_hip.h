@@ -463,6 +463,26 @@ int l2s_mel_spectrogram(const void* wav, int wav_is_i16, int64_t ldw, const int3
                         int n_mels, float floor_, void* stream);
 
 /*
+ * The same analysis with the frame placement and the magnitude's epsilon as arguments - what the HiFi-GAN mel_spectrogram of the
+ * vocoder's training and validation loss needs (speech-resynthesis/dataset.py:44-67 with configs/lrs3/multi_input.json:
+ * n_fft 1024, hop 256, window 1024, 80 bands, 0 Hz .. sr/2; F.pad(reflect, (n_fft - hop) / 2) then torch.stft(center=False),
+ * sqrt(re^2 + im^2 + 1e-9), the librosa Slaney filterbank, log(clamp(., 1e-5)); called at multi_input_vocoder/train.py:152,224 and
+ * dataset_multi_input.py:275).  The arguments of l2s_mel_spectrogram plus
+ *   pad: reflect padding on each side, 0 <= pad <= n_fft/2.  Frame t of clip b covers samples [t*hop - pad, t*hop - pad + n_fft),
+ *     reflected against the clip's own n_b; T_b = (n_b + 2 pad - n_fft) / hop + 1 frames when n_b > pad and n_b + 2 pad >= n_fft,
+ *     else 0 (no valid reflection, or not one whole frame); rows T_b <= t < T_rows are zeros; every clip is analysed alone;
+ *   mag_eps >= 0: mag = sqrtf((re*re + im*im) + mag_eps), squares not contracted.
+ * wav (int16 or fp32), n_samples, the packed basis [n_fft][n_fft] with its column map (the real part of bin n_fft/2 in column 32),
+ * fb / fb_range, the time-major output with ldm, the clamp floor_, logf and the alignment and shape checks are those documented
+ * above.  Same kernel template (csrc/melspec.hip): l2s_mel_spectrogram is this entry at (640, 160, pad 320, mag_eps 0).
+ * Supported: (n_fft, hop) = (1024, 256) and (640, 160), n_mels = 80; other sizes, a pad outside [0, n_fft/2] or a negative mag_eps
+ * return L2S_EUNSUPPORTED.  B <= 65535, T_rows <= 2^22.
+ */
+int l2s_stft_mel(const void* wav, int wav_is_i16, int64_t ldw, const int32_t* n_samples, int B, int S, const float* basis,
+                 const float* fb, const int32_t* fb_range, float* mel, int ldm, int T_rows, int n_fft, int hop, int n_mels,
+                 int pad, float mag_eps, float floor_, void* stream);
+
+/*
  * Forward (scoring) half of the `multi_target` criterion (multi_target_lip2speech/criterion.py), csrc/criterion.hip.  All three
  * entries write PER-CLIP results that depend on that clip's rows alone (no atomics, fixed reduction order: the same bytes for a
  * clip whatever its batch mates and from run to run); batch totals are the caller's sum over clips in index order.  Terms are

@@ -106,6 +106,7 @@ SIGNATURES = {
     "l2s_respair_final": ([ctypes.POINTER(RespairFinalDesc), _vp], _i),
     "l2s_preprocess_frames": ([_vp, _vp, _i, _i, _i, _i, _i, _f, _f, _i, _vp], _i),
     "l2s_mel_spectrogram": ([_vp, _i, ctypes.c_int64, _vp, _i, _i, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _f, _vp], _i),
+    "l2s_stft_mel": ([_vp, _i, ctypes.c_int64, _vp, _i, _i, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _f, _f, _vp], _i),
     "l2s_unit_ce": ([_vp, _i, _vp, _i, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp], _i),
     "l2s_mel_l1_sc": ([_vp, _i, _vp, _i, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp], _i),
     "l2s_ctc_loss_workspace": ([_i, _i, _i], ctypes.c_size_t),

@@ -73,22 +73,15 @@ def num_frames(n_samples, hop=160):
     return 1 + n_samples // hop
 
 
-class TacotronSTFT:
-    """`TacotronSTFT(...).mel_spectrogram(audio)` of extract_mel_spec, on the device; defaults from config.py:21-27."""
+def band_ranges(fb):
+    """int32 [n_mels, 2]: [first, past-last) bin of each band's non-zero weights (0, 0 for an empty band)."""
+    nz = fb != 0
+    return np.stack([np.where(nz.any(1), nz.argmax(1), 0), np.where(nz.any(1), fb.shape[1] - nz[:, ::-1].argmax(1), 0)],
+                    axis=1).astype(np.int32)
 
-    def __init__(self, filter_length=640, hop_length=160, win_length=640, n_mel_channels=80, sampling_rate=16000, mel_fmin=0.0,
-                 mel_fmax=8000.0, floor=1e-5):
-        if win_length != filter_length:
-            raise ValueError("win_length must equal filter_length")
-        self.n_fft, self.hop, self.n_mels, self.sr, self.floor = filter_length, hop_length, n_mel_channels, sampling_rate, floor
-        self.basis = packed_basis(filter_length).astype(np.float32)
-        fb = mel_filterbank(sampling_rate, filter_length, n_mel_channels, mel_fmin, mel_fmax)
-        self.fb = fb.astype(np.float32)
-        nbin = filter_length // 2 + 1
-        nz = self.fb != 0
-        self.fb_range = np.stack([np.where(nz.any(1), nz.argmax(1), 0),
-                                  np.where(nz.any(1), nbin - nz[:, ::-1].argmax(1), 0)], axis=1).astype(np.int32)
-        self._dev = {}
+
+class _DeviceTables:
+    """basis / fb / fb_range as float32 / int32 numpy arrays on the instance, uploaded once per device."""
 
     def tables(self, device):
         """(basis, fb, fb_range) on `device`, uploaded once per device."""
@@ -99,6 +92,39 @@ class TacotronSTFT:
         if key not in self._dev:
             self._dev[key] = tuple(torch.from_numpy(t).to(device) for t in (self.basis, self.fb, self.fb_range))
         return self._dev[key]
+
+    def _lengths(self, wav, n_samples, least):
+        """n_samples of mel_rows -> None or an int32 device tensor [B]; a host sequence is checked: least < n <= S."""
+        B, S = wav.shape
+        if n_samples is None:
+            if S <= least:
+                raise ValueError(f"reflect padding needs more than {least} samples, got {S}")
+            return None
+        if isinstance(n_samples, torch.Tensor) and n_samples.is_cuda:
+            if n_samples.dtype != torch.int32 or n_samples.shape != (B,):
+                raise ValueError("n_samples: int32 [B]")
+            return n_samples.contiguous()
+        ns = [int(v) for v in (n_samples.tolist() if hasattr(n_samples, "tolist") else n_samples)]
+        if len(ns) != B:
+            raise ValueError("n_samples: one length per clip")
+        if any(v <= least or v > S for v in ns):
+            raise ValueError(f"n_samples: every clip needs {least} < n <= {S} samples, got {ns}")
+        return torch.tensor(ns, dtype=torch.int32).to(wav.device)
+
+
+class TacotronSTFT(_DeviceTables):
+    """`TacotronSTFT(...).mel_spectrogram(audio)` of extract_mel_spec, on the device; defaults from config.py:21-27."""
+
+    def __init__(self, filter_length=640, hop_length=160, win_length=640, n_mel_channels=80, sampling_rate=16000, mel_fmin=0.0,
+                 mel_fmax=8000.0, floor=1e-5):
+        if win_length != filter_length:
+            raise ValueError("win_length must equal filter_length")
+        self.n_fft, self.hop, self.n_mels, self.sr, self.floor = filter_length, hop_length, n_mel_channels, sampling_rate, floor
+        self.basis = packed_basis(filter_length).astype(np.float32)
+        fb = mel_filterbank(sampling_rate, filter_length, n_mel_channels, mel_fmin, mel_fmax)
+        self.fb = fb.astype(np.float32)
+        self.fb_range = band_ranges(self.fb)
+        self._dev = {}
 
     def mel_rows(self, wav, n_samples=None):
         """wav: device tensor [B, S], fp32 in (-1, 1) or int16 PCM.  n_samples: clip lengths - None (all S), a host sequence
@@ -111,20 +137,7 @@ class TacotronSTFT:
         B, S = wav.shape
         if wav.stride(1) != 1:
             wav = wav.contiguous()
-        if n_samples is None:
-            if S <= self.n_fft // 2:
-                raise ValueError(f"reflect padding needs more than {self.n_fft // 2} samples, got {S}")
-        elif isinstance(n_samples, torch.Tensor) and n_samples.is_cuda:
-            if n_samples.dtype != torch.int32 or n_samples.shape != (B,):
-                raise ValueError("n_samples: int32 [B]")
-            n_samples = n_samples.contiguous()
-        else:
-            ns = [int(v) for v in (n_samples.tolist() if hasattr(n_samples, "tolist") else n_samples)]
-            if len(ns) != B:
-                raise ValueError("n_samples: one length per clip")
-            if any(v <= self.n_fft // 2 or v > S for v in ns):
-                raise ValueError(f"n_samples: every clip needs {self.n_fft // 2} < n <= {S} samples, got {ns}")
-            n_samples = torch.tensor(ns, dtype=torch.int32).to(wav.device)
+        n_samples = self._lengths(wav, n_samples, self.n_fft // 2)
         basis, fb, fb_range = self.tables(wav.device)
         T = num_frames(S, self.hop)
         mel = torch.empty(B, T, self.n_mels, device=wav.device, dtype=torch.float32)
@@ -135,6 +148,55 @@ class TacotronSTFT:
     def mel_spectrogram(self, audio):
         """audio [B, S] in (-1, 1) -> [B, n_mel, T], the call extract_mel_spec makes."""
         return self.mel_rows(audio).transpose(1, 2)
+
+
+class MelSpectrogram(_DeviceTables):
+    """The HiFi-GAN `mel_spectrogram(y, n_fft, num_mels, sampling_rate, hop_size, win_size, fmin, fmax, center=False)` of the
+    vocoder's loss (speech-resynthesis/dataset.py:44-67; train.py:152,224 and dataset_multi_input.py:275 call it with the sizes of
+    configs/lrs3/multi_input.json and fmax = fmax_for_loss = null, i.e. sr/2), on the device: reflect pad (n_fft - hop_size) // 2 on
+    each side, periodic Hann window, torch.stft(center=False), sqrt(re^2 + im^2 + 1e-9), the Slaney filterbank, log(clamp(., 1e-5)).
+    Tables are float64, rounded to float32 once, uploaded once per device.  There is no CPU path."""
+
+    def __init__(self, n_fft=1024, num_mels=80, sampling_rate=16000, hop_size=256, win_size=1024, fmin=0, fmax=None):
+        if win_size != n_fft:
+            raise ValueError("win_size must equal n_fft")
+        self.n_fft, self.hop, self.n_mels, self.sr = n_fft, hop_size, num_mels, sampling_rate
+        self.pad, self.mag_eps, self.floor = (n_fft - hop_size) // 2, 1e-9, 1e-5
+        self.basis = packed_basis(n_fft).astype(np.float32)
+        fmax = sampling_rate / 2.0 if fmax is None else fmax
+        self.fb = mel_filterbank(sampling_rate, n_fft, num_mels, float(fmin), float(fmax)).astype(np.float32)
+        self.fb_range = band_ranges(self.fb)
+        self._dev = {}
+
+    def num_frames(self, n_samples):
+        """Frames of a clip of n_samples: 0 unless the reflection is valid (n > pad) and one whole frame fits."""
+        n = int(n_samples)
+        return (n + 2 * self.pad - self.n_fft) // self.hop + 1 if n > self.pad and n + 2 * self.pad >= self.n_fft else 0
+
+    def mel_rows(self, wav, n_samples=None):
+        """wav: device tensor [B, S], fp32 in (-1, 1) or int16 PCM.  n_samples: clip lengths - None (all S), a host sequence
+        (checked: pad < n <= S) or an int32 device tensor (not read on the host).  Returns fp32 [B, num_frames(S), n_mel]; clip
+        b's rows past num_frames(n_b) are zeros."""
+        if not isinstance(wav, torch.Tensor) or not wav.is_cuda:
+            raise L2SError("mel_rows: expected a device tensor (there is no CPU path)")
+        if wav.dim() != 2:
+            raise ValueError("wav: [B, S]")
+        B, S = wav.shape
+        if wav.stride(1) != 1:
+            wav = wav.contiguous()
+        T = self.num_frames(S)
+        if T <= 0:
+            raise ValueError(f"no frame fits: {S} samples with n_fft {self.n_fft} and {self.pad} reflected on each side")
+        n_samples = self._lengths(wav, n_samples, self.pad)
+        basis, fb, fb_range = self.tables(wav.device)
+        mel = torch.empty(B, T, self.n_mels, device=wav.device, dtype=torch.float32)
+        ops.stft_mel(wav, mel, basis, fb, fb_range, B=B, S=S, T_rows=T, n_samples=n_samples, ldw=wav.stride(0) if B > 1 else S,
+                     n_fft=self.n_fft, hop=self.hop, n_mels=self.n_mels, pad=self.pad, mag_eps=self.mag_eps, floor=self.floor)
+        return mel
+
+    def __call__(self, y):
+        """y [B, S] in (-1, 1) -> [B, n_mel, T], the call the reference makes."""
+        return self.mel_rows(y).transpose(1, 2)
 
 
 _default = None

@@ -10,6 +10,7 @@ Video decode itself is outside the path: mp4 is read with Op
 sibling `<clip>.npy` uint8 [T,H,W] array is used; nothing else is attempted.
 """
 import os
+import random
 import wave
 from typing import List
 
@@ -228,13 +229,28 @@ def audio_num_samples(path, pad=None):
 
 class MelCodeDataset:
     def __init__(self, file_list, code_hop_size=320, mel_hop_size=160, code_dict_path=None, pad=None, mel_from_audio=False,
-                 stft=None):
+                 stft=None, segment_size=None, seed=1234, load_audio=False, sampling_rate=16000):
         """mel_from_audio: the mel/ directory is not touched - the wav is read, zero-extended to the padded length and analysed
-        on the device (audio.TacotronSTFT, or `stft`: anything with its mel_rows) before the same trimming rule applies."""
+        on the device (audio.TacotronSTFT, or `stft`: anything with its mel_rows) before the same trimming rule applies.
+
+        segment_size (None: today's inference items, audio not read unless load_audio): the training / validation items of
+        dataset_multi_input.py:198-291.  The wav is read as int16 (another sampling rate is refused: there is no resampler here),
+        taken as value / 32768 in float64, divided by its peak and multiplied by 0.95 (:211-212, librosa.util.normalize on a 1-d
+        signal), trimmed with code and mel (:219-241), and while it is shorter than the segment audio, code and mel are doubled
+        (:249-255).  Then _sample_interval (speech-resynthesis/dataset.py:199-219) cuts the same stretch out of all three: with
+        the sequences audio / code / mel the common step is code_hop_size samples and start = randint(0, L - segment_size //
+        code_hop_size) code frames, ONE draw per __getitem__ call - so reading the items once in index order reproduces the
+        reference's draws.  They come from a random.Random(seed) owned by this object; the reference seeds the module-level
+        generator in its constructor (:154), an instance keeps other users of `random` out of the sequence.  segment_size <= 0:
+        the whole clip, start 0, no draw.  Items are (feats, audio float32 [segment], filename, None); `starts[index]` keeps the
+        start of the last read in code frames.  Note that `split=False` at train.py:117 has no effect in the reference -
+        __getitem__ never reads it - so its validation does run on random 8960-sample segments, and so does this."""
         self.audio_files, self.mel_files, self.codes = file_list[:3]
         self.mel_from_audio, self.stft = mel_from_audio, stft
         self.t_labels = file_list[3] if len(file_list) > 3 else None   # text supervision (dataset_multi_input.py:225-239)
         self.code_hop_size, self.mel_hop_size, self.pad = code_hop_size, mel_hop_size, pad
+        self.segment_size, self.load_audio, self.sampling_rate = segment_size, load_audio or segment_size is not None, sampling_rate
+        self.rng, self.starts = random.Random(seed), {}
         self.code_dict = load_code_dict(code_dict_path)
         self.speaker_emb_files = [f.replace("/audio/", "/spk_emb/")[:-4] + ".npy" for f in self.audio_files]
 
@@ -273,8 +289,39 @@ class MelCodeDataset:
         code = code[: cut // self.code_hop_size]
         assert cut // self.code_hop_size == code.shape[0], "Code audio mismatch"
         assert cut // self.mel_hop_size == mel.shape[0], "Mel audio mismatch"
-        feats = {"code": code.astype(np.int64), "mel": np.ascontiguousarray(mel.transpose(1, 0)).astype(np.float32),
+        mel = mel.transpose(1, 0)
+        wav = None
+        if self.load_audio:
+            wav, code, mel, t_label = self._segment(index, filename, n_audio, cut, code, mel,
+                                                    None if t_label is None else t_label[: cut // self.code_hop_size])
+        feats = {"code": code.astype(np.int64), "mel": np.ascontiguousarray(mel).astype(np.float32),
                  "spkr": np.load(self.speaker_emb_files[index]).astype(np.float32)}
         if t_label is not None:
-            feats["t_label"] = t_label[: cut // self.code_hop_size]
-        return feats, None, str(filename), None
+            feats["t_label"] = t_label[: cut // self.code_hop_size] if wav is None else t_label
+        return feats, wav, str(filename), None
+
+    def _segment(self, index, filename, n_audio, cut, code, mel, t_label):
+        """The audio side of dataset_multi_input.py:201-273 (see __init__): returns (audio float32, code, mel [80, .], t_label)."""
+        from . import audio as _audio
+        pcm = _audio.read_wav_s16(filename, self.sampling_rate)
+        x = np.zeros(n_audio, np.float64)                                     # :208-210 --pad zero-extends
+        x[: pcm.shape[0]] = pcm
+        x = x / 32768.0
+        peak = np.abs(x).max()
+        x = (x / peak if peak > 0 else x) * 0.95                              # :211-212
+        x = x[:cut]                                                           # :239
+        seg = self.segment_size if self.segment_size is not None else -1
+        while x.shape[0] < seg:                                               # :249-255
+            x, code, mel = np.hstack([x, x]), np.hstack([code, code]), np.hstack([mel, mel])
+            if t_label is not None:
+                t_label = np.hstack([t_label, t_label])
+        x = x.astype(np.float32)                                              # :257 torch.FloatTensor
+        seqs = [x, code, mel] + ([t_label] if t_label is not None else [])
+        N = max(v.shape[-1] for v in seqs)                                    # speech-resynthesis/dataset.py:199-219
+        seq_len = seg if seg > 0 else N
+        hops = [N // v.shape[-1] for v in seqs]
+        lcm = int(np.lcm.reduce(hops))
+        start = self.rng.randint(0, N // lcm - seq_len // lcm) if seg > 0 else 0
+        self.starts[index] = start
+        out = [v[..., start * (lcm // hp): (start + seq_len // lcm) * (lcm // hp)] for v, hp in zip(seqs, hops)]
+        return out[0], out[1], out[2], (out[3] if t_label is not None else None)

@@ -553,6 +553,32 @@ def mel_spectrogram(wav, mel, basis, fb, fb_range, *, B, S, T_rows, n_samples=No
         flops=2.0 * frames * n_fft * n_fft, nbytes=float(B) * S * wav.element_size() + 4.0 * frames * n_mels + 4.0 * n_fft * n_fft)
 
 
+def stft_mel(wav, mel, basis, fb, fb_range, *, B, S, T_rows, n_fft, hop, pad, mag_eps=0.0, n_samples=None, ldw=None, ldm=None, n_mels=80,
+             floor=1e-5):
+    """mel_spectrogram with the frame placement (`pad` reflected samples on each side) and the magnitude's epsilon as arguments, at
+    (n_fft, hop) = (1024, 256) or (640, 160): the HiFi-GAN analysis of the vocoder's loss (audio.MelSpectrogram builds the tables).
+    Clip b has (n_b + 2 pad - n_fft) // hop + 1 rows (0 unless n_b > pad and a whole frame fits); the rest of its T_rows are zeros."""
+    if wav.dtype not in (torch.float32, torch.int16):
+        raise L2SError(f"wav: expected float32 or int16, got {wav.dtype}")
+    if n_samples is not None and n_samples.dtype != torch.int32:
+        raise L2SError("n_samples must be int32")
+    _req(wav, None, "wav"), _req(mel, torch.float32, "mel"), _req(basis, torch.float32, "basis"), _req(fb, torch.float32, "fb")
+    _req(fb_range, torch.int32, "fb_range")
+    ldw = ldw if ldw is not None else S
+    ldm = ldm if ldm is not None else n_mels
+    if (B - 1) * ldw + S > _extent(wav) or ((B * T_rows - 1) * ldm + n_mels) > _extent(mel):
+        raise L2SError("stft_mel: wav smaller than [B, ldw] or mel smaller than [B, T_rows, ldm]")
+    if basis.numel() < n_fft * n_fft or fb.numel() < n_mels * (n_fft // 2 + 1) or fb_range.numel() < 2 * n_mels:
+        raise L2SError("stft_mel: tables smaller than [n_fft, n_fft], [n_mels, n_fft/2 + 1], [n_mels, 2]")
+    if n_samples is not None and n_samples.numel() < B:
+        raise L2SError("stft_mel: n_samples shorter than B")
+    frames = float(B) * T_rows
+    _run("l2s_stft_mel", lambda: _lib.load().l2s_stft_mel(
+        _ptr(wav), int(wav.dtype == torch.int16), ldw, _ptr(n_samples), B, S, _ptr(basis), _ptr(fb), _ptr(fb_range), _ptr(mel), ldm,
+        T_rows, n_fft, hop, n_mels, pad, float(mag_eps), float(floor), _stream()),
+        flops=2.0 * frames * n_fft * n_fft, nbytes=float(B) * S * wav.element_size() + 4.0 * frames * n_mels + 4.0 * n_fft * n_fft)
+
+
 def unit_ce(logits, target, nll, smooth, n_correct, n_tok, *, B, T2, V, ldl=None, ldt=None, lens=None, len_mul=2, pad_idx=1,
             ignore_prefix=0):
     """Label-smoothed cross-entropy sums and accuracy counts per clip in one pass over fp32 logits [B*T2, ldl] (csrc/criterion.hip):
@@ -884,6 +910,9 @@ _SCHEMAS = {
     "mel_spectrogram": "(Tensor wav, Tensor(a!) mel, Tensor basis, Tensor fb, Tensor fb_range, *, int B, int S, int T_rows, "
                        "Tensor? n_samples=None, int? ldw=None, int? ldm=None, int n_fft=640, int hop=160, int n_mels=80, "
                        "float floor=1e-05) -> ()",
+    "stft_mel": "(Tensor wav, Tensor(a!) mel, Tensor basis, Tensor fb, Tensor fb_range, *, int B, int S, int T_rows, int n_fft, int hop, "
+                "int pad, float mag_eps=0.0, Tensor? n_samples=None, int? ldw=None, int? ldm=None, int n_mels=80, "
+                "float floor=1e-05) -> ()",
     "unit_ce": "(Tensor logits, Tensor target, Tensor(a!) nll, Tensor(b!) smooth, Tensor(c!) n_correct, Tensor(d!) n_tok, *, int B, "
                "int T2, int V, int? ldl=None, int? ldt=None, Tensor? lens=None, int len_mul=2, int pad_idx=1, "
                "int ignore_prefix=0) -> ()",
