@@ -320,7 +320,10 @@ int launch_patch(const l2s_gemm_desc& d, hipStream_t st) {
     const int64_t npos = imgs * (d.Hi + 2) * (d.Wi + 2);
     ntiles = (int)((npos + PBM - 1) / PBM);
   }
-  constexpr int slots = CH == 64 ? 512 : 256;   // resident blocks: two per CU at 64 channels, one at 128
+  constexpr int resident = CH == 64 ? 512 : 256;   // resident blocks: two per CU at 64 channels, one at 128
+  // test / tuning aid: a smaller grid, so that a small problem makes a block walk several tiles
+  static const int slots_env = [] { const char* e = getenv("L2S_PATCH_SLOTS"); return e ? atoi(e) : 0; }();
+  const int slots = slots_env >= 1 && slots_env < resident ? slots_env : resident;
   const int grid = ntiles < slots ? ntiles : slots;
   hipLaunchKernelGGL(kern, dim3(grid), dim3(CH * 4), QSMEM, st, d, ntiles, tiles_per_clip, lo);
   L2S_CHECK_LAUNCH();
@@ -335,12 +338,15 @@ extern "C" int l2s_debug_patch_stamps(void* buf) { return (int)hipMemcpyToSymbol
 // Does this descriptor fit the patch kernel?  (called by l2s_tapgemm before the generic path)
 bool l2s_patchconv_eligible(const l2s_gemm_desc& d) {
   static const int ch128 = [] { const char* e = getenv("L2S_PATCH128"); return e ? atoi(e) : 1; }();   // A/B switch
+  // the row threshold is a measured-speed condition (below it the generic tiles are as fast); L2S_PATCH_MIN_M replaces it so that
+  // tests reach this kernel at small shapes (test / tuning aid; values < 1 are ignored).  Every other condition is about correctness.
+  static const int64_t min_m = [] { const char* e = getenv("L2S_PATCH_MIN_M"); const long v = e ? atol(e) : 0; return v >= 1 ? (int64_t)v : (int64_t)64 * 1024; }();
   if (!((d.Cin == 64 && d.N == 64) || (ch128 && d.Cin == 128 && d.N == 128)) || (d.groups > 1)) return false;
   if (d.mode == L2S_MODE_CONV1D) {
     if (d.stride != 1 || d.T_out != d.T_in || d.ntaps < 2 || d.M % d.T_out) return false;
     const int a = d.off, b = (d.ntaps - 1) * d.dil + d.off;
     const int lo = a < b ? a : b, hi = a < b ? b : a;
-    return (hi - lo) <= PROWS - PBM && lo <= 0 && hi >= 0 && (int64_t)d.M >= 64 * 1024;
+    return (hi - lo) <= PROWS - PBM && lo <= 0 && hi >= 0 && (int64_t)d.M >= min_m;
   }
   if (d.mode == L2S_MODE_CONV2D) {
     if (d.stride != 1 || d.KW != 3 || d.ntaps != 9 || d.pad != 1 || d.Ho != d.Hi || d.Wo != d.Wi) return false;
@@ -348,7 +354,7 @@ bool l2s_patchconv_eligible(const l2s_gemm_desc& d) {
     // the padded-flattened position space computes (H+2)(W+2) positions per image: 1.19x at 22x22, 1.40x at 11x11,
     // where the generic kernel measured 17 % faster
     if (4 * (d.Hi + 2) * (d.Wi + 2) > 5 * d.Hi * d.Wi) return false;
-    return 2 * (d.Wi + 3) <= PROWS - PBM && (int64_t)d.M >= 64 * 1024;
+    return 2 * (d.Wi + 3) <= PROWS - PBM && (int64_t)d.M >= min_m;
   }
   return false;
 }

@@ -469,6 +469,13 @@ __global__ __launch_bounds__(512) void phasegemm_kernel(const l2s_gemm_desc p, c
 #endif
 }
 
+// Resident blocks per XCD (32 = one per CU).  L2S_PHASE_SLOTS is a test / tuning aid: with fewer slots a small problem makes a
+// block walk several output tiles; values < 1 or > 32 are ignored.
+inline int phase_slots_cap() {
+  static const int env = [] { const char* e = getenv("L2S_PHASE_SLOTS"); return e ? atoi(e) : 0; }();
+  return env >= 1 && env < 32 ? env : 32;
+}
+
 template <typename ET, int MODE, int EPI>
 int launch_phase(const l2s_gemm_desc& d, hipStream_t st) {
   auto kern = phasegemm_kernel<ET, MODE, EPI>;
@@ -477,7 +484,8 @@ int launch_phase(const l2s_gemm_desc& d, hipStream_t st) {
   const int tilesM = (d.M + PBM - 1) / PBM, tilesN = (d.N + PBN - 1) / PBN;
   const int ntiles = tilesM * tilesN * (MODE == PG_KTAB ? d.groups : 1);
   const int chunk = (ntiles + 7) / 8;
-  const int slots = chunk < 32 ? chunk : 32;
+  const int slots_cap = phase_slots_cap();
+  const int slots = chunk < slots_cap ? chunk : slots_cap;
   const double ap = (double)PBM * d.Cin * 2.0, wp = (double)PBN * d.Cin * d.ntaps * 2.0;
   auto cdivi = [](int a, int b) { return (a + b - 1) / b; };
   int band = 1;

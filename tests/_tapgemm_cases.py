@@ -8,6 +8,9 @@ Pure Python: no torch, no GPU, no library.  A case is a dict
 `geom` describes the operands and the oracle op, `epi` the epilogue; `descriptors(case)` turns both into the integer fields of
 l2s_gemm_desc (one dict per launch: a ConvTranspose1d case is one launch per output phase).  Shapes are functions of the forced
 block tile (BM, BN), so that every tile sees interior full wave tiles and ragged edge tiles in one launch.
+
+The parts of PART_ENV are the same for the two specialised kernels (phase-staggered 256 x 256, LDS patch): their cases also carry
+`kernel` and `inst`, and the child process of a part runs under the switches PART_ENV names.
 """
 
 # ---- constants of include/lip2speech_hip.h (tests/test_tapgemm_matrix_cpu.py checks them against the binding) -------------------
@@ -143,10 +146,13 @@ def g_conv1d(M, N, Cin, k, dil, **kw):
     return _geom("conv1d", MODE_CONV1D, M, N, Cin, k, k=k, dil=dil, off=-((k - 1) * dil // 2), B=B, T=T, **kw)
 
 
-def g_conv2d(M, N, Cin, H, stride, **kw):
-    """3 x 3, padding 1, on H x H maps; the launch computes the first M rows of the (image, y, x) space."""
+def g_conv2d(M, N, Cin, H, stride, W=None, **kw):
+    """3 x 3, padding 1, on H x H maps (H x W where W is given); the launch computes the first M rows of the (image, y, x) space."""
     Ho = (H + 2 - 3) // stride + 1
-    return _geom("conv2d", MODE_CONV2D, M, N, Cin, 9, H=H, Ho=Ho, stride=stride, nimg=cdiv(M, Ho * Ho), **kw)
+    if W is None:
+        return _geom("conv2d", MODE_CONV2D, M, N, Cin, 9, H=H, Ho=Ho, stride=stride, nimg=cdiv(M, Ho * Ho), **kw)
+    Wo = (W + 2 - 3) // stride + 1
+    return _geom("conv2d", MODE_CONV2D, M, N, Cin, 9, H=H, Ho=Ho, Wi=W, Wo=Wo, stride=stride, nimg=cdiv(M, Ho * Wo), **kw)
 
 
 def g_convt(B, L, N, Cin, k=8, s=4, **kw):
@@ -265,7 +271,273 @@ def band_cases():
     return cases
 
 
+# ---- the two specialised kernels: phase-staggered 256 x 256 (csrc/phasegemm_kernel.h) and LDS patch (csrc/patchconv.hip) ------------
+# A case of these parts also carries `kernel` (what l2s_tapgemm_variant must answer) and `inst`, the instantiation it claims:
+# (dt, mode, EPI) of phasegemm_kernel, (dt, mode, CH, EPI) of patchconv64_kernel.
+PHASE, PATCH64, PATCH128 = 256256, 999064, 999128
+EPI_G16A, EPI_G16B, EPI_S32, EPI_ALL, EPI_X32 = 6, 7, 8, 9, 10
+PHASE_EPIS = (0, 1, 2, 3, 4, 5, EPI_G16A, EPI_G16B, EPI_S32, EPI_X32)      # launch_phase_mode
+PATCH_EPIS = (2, 3, EPI_G16A, EPI_G16B, EPI_ALL)                           # launch_patch_epi
+PHASE_SLOTS, PATCH_SLOTS = 2, 4                                            # the slot caps of the walk parts
+# every switch a part's child process depends on: those named here are set to these values, the others are unset
+SWITCHES = ("L2S_FORCE_TILE", "L2S_BAND", "L2S_PHASEGEMM", "L2S_PHASEGEMM_RES", "L2S_PHASE_SLOTS", "L2S_NO_PATCHCONV",
+            "L2S_PATCH128", "L2S_PATCH_SLOTS", "L2S_PATCH_MIN_M")
+_PH, _PA = dict(L2S_PHASEGEMM="2"), dict(L2S_PATCH_MIN_M="1", L2S_PHASEGEMM="0")
+PART_ENV = {"phase-families": _PH, "phase-walk": dict(_PH, L2S_PHASE_SLOTS=str(PHASE_SLOTS)), "phase-natural": _PH,
+            "patch-families": _PA, "patch-walk": dict(_PA, L2S_PATCH_SLOTS=str(PATCH_SLOTS)), "patch-natural": _PA}
+PART_KERNELS = {"phase-families": (PHASE,), "phase-walk": (PHASE,), "phase-natural": (PHASE,),
+                "patch-families": (PATCH64, PATCH128), "patch-walk": (PATCH64, PATCH128), "patch-natural": (PATCH64,)}
+
+
+def is_x32(flags, act):
+    """csrc/tapgemm_tiles.h::is_x32, restated."""
+    need, may = F_RES_POST | F_OUT_F32, F_ACCUM | F_DUAL | F_MASK
+    return act == ACT_NONE and flags & need == need and flags & ~(need | may) == 0
+
+
+def x32_epilogues():
+    """The ResBlock-sum update of the phase kernel: fp32 out + 16-bit residual after no activation; pick_epilogue family 9."""
+    kw = dict(res="16", when="post", out32=True)
+    E = [epi("x32+mask", 9, mask=True, **kw), epi("x32+accum", 9, accum=True, **kw),
+         epi("x32+accum+dual+mask", 9, accum=True, dual=True, mask=True, **kw), epi("x32+dual", 9, dual=True, **kw)]
+    assert all(is_x32(e["flags"], e["act"]) for e in E)
+    return E
+
+
+def _named(names):
+    table = {e["name"]: e for e in family_epilogues() + x32_epilogues()}
+    return [table[n] for n in names]
+
+
+def phase_epi(e, N=0):
+    """EPI of the phasegemm_kernel instantiation launch_phase_mode picks, None where l2s_phasegemm_eligible declines: family 9
+    but for X32, and families 0-6 (whole 8-channel groups stored from the MFMA layout) at N % 8 != 0."""
+    if e["family"] <= EPI_G16A:
+        return e["family"] if N % 8 == 0 else None
+    if e["family"] < EPI_ALL:
+        return e["family"]
+    return EPI_X32 if is_x32(e["flags"], e["act"]) else None
+
+
+def patch_epi(e):
+    return {0: 2, 1: 3, 2: 2, 3: 3, EPI_G16A: EPI_G16A, EPI_G16B: EPI_G16B}.get(e["family"], EPI_ALL)
+
+
+def phase_band(M, N, Cin, ntaps):
+    """launch_phase's band height (the operand-footprint minimum over b = 1 .. tilesM, first minimum wins), restated."""
+    tilesM, tilesN = cdiv(M, 256), cdiv(N, 256)
+    chunk = cdiv(tilesM * tilesN, 8)
+    ap, wp = 256.0 * Cin * 2.0, 256.0 * Cin * ntaps * 2.0
+    band, best = 1, 1e300
+    for b in range(1, tilesM + 1):
+        wn = min(cdiv(chunk, b), tilesN)
+        an = b * cdiv(chunk, b * tilesN)
+        fp = ap * min(an, tilesM) + wp * wn
+        if fp < best:
+            best, band = fp, b
+    return band
+
+
+def phase_schedule(M, N, slots_cap=32):
+    """(ntiles, chunk, slots, my_n of every block [xcd][slot]) of launch_phase / phasegemm_kernel."""
+    ntiles = cdiv(M, 256) * cdiv(N, 256)
+    chunk = cdiv(ntiles, 8)
+    slots = min(chunk, slots_cap)
+    my_n = []
+    for x in range(8):
+        lo = x * chunk
+        hi = min(lo + chunk, ntiles)
+        my_n.append([(hi - lo - s + slots - 1) // slots if lo + s < hi else 0 for s in range(slots)])
+    return ntiles, chunk, slots, my_n
+
+
+def patch_schedule(g, ch, slots_cap=None):
+    """(ntiles, grid, tiles of every block) of launch_patch / patchconv64_kernel; a CONV1D tile is (clip, first frame), a CONV2D
+    tile the first padded-flattened position."""
+    if g["mode"] == MODE_CONV1D:
+        per_clip = cdiv(g["T"], 256)
+        ntiles = (g["M"] // g["T"]) * per_clip
+        tile = lambda L: (L // per_clip, (L % per_clip) * 256)
+    else:
+        H, W = g["H"], g.get("Wi", g["H"])
+        ntiles = cdiv((g["M"] // (H * W)) * (H + 2) * (W + 2), 256)
+        tile = lambda L: L * 256
+    resident = 512 if ch == 64 else 256
+    grid = min(ntiles, slots_cap if slots_cap and 1 <= slots_cap < resident else resident)
+    return ntiles, grid, [[tile(L) for L in range(b, ntiles, grid)] for b in range(grid)]
+
+
+def patch_eligible(d):
+    """l2s_patchconv_eligible without its measured-speed row threshold: the conditions that are about correctness."""
+    if not ((d["Cin"], d["N"]) in ((64, 64), (128, 128)) and d["groups"] == 1):
+        return False
+    if d["mode"] == MODE_CONV1D:
+        if d["stride"] != 1 or d["T_out"] != d["T_in"] or d["ntaps"] < 2 or d["M"] % d["T_out"]:
+            return False
+        a, b = d["off"], (d["ntaps"] - 1) * d["dil"] + d["off"]
+        return max(a, b) - min(a, b) <= 64 and min(a, b) <= 0 <= max(a, b)
+    if d["mode"] == MODE_CONV2D:
+        if d["stride"] != 1 or d["KW"] != 3 or d["ntaps"] != 9 or d["pad"] != 1 or d["Ho"] != d["Hi"] or d["Wo"] != d["Wi"]:
+            return False
+        if d["M"] % (d["Hi"] * d["Wi"]) or 4 * (d["Hi"] + 2) * (d["Wi"] + 2) > 5 * d["Hi"] * d["Wi"]:
+            return False
+        return 2 * (d["Wi"] + 3) <= 64
+    return False
+
+
+def _case(name, dt, g, e, kernel, ch=None):
+    ep = phase_epi(e, g["N"]) if kernel == PHASE else patch_epi(e)
+    assert ep is not None, (name, e["name"])
+    inst = (dt, g["mode"], ep) if kernel == PHASE else (dt, g["mode"], ch, ep)
+    return dict(name=f"{name}/{e['name']}", dt=dt, mode=g["mode"], uni=g["uni"], family=e["family"], geom=g, epi=e,
+                kernel=kernel, inst=inst)
+
+
+def _phase_conv_geoms(M, N4, N8, B):
+    """The conv-mode geometries of the phase parts at N4 (N % 8 == 4: families 7, 8 and X32) and at N8 (N % 8 == 0: every family)."""
+    out = []
+    for n in dict.fromkeys((N4, N8)):
+        sfx = f"-n{n}"
+        out += [("conv1d-k3" + sfx, g_conv1d(M, n, 64, 3, 1)), ("conv1d-c128-k5d3" + sfx, g_conv1d(M, n, 128, 5, 3)),
+                ("conv2d-7x7" + sfx, g_conv2d(M, n, 64, 7, 1)), ("conv2d-13x13s2" + sfx, g_conv2d(M, n, 64, 13, 2)),
+                ("convt-k8s4" + sfx, g_convt(B, M // B, n, 64, 8, 4)), ("convt-k11s5" + sfx, g_convt(B, M // B, n, 64, 11, 5))]
+    return out
+
+
+def phase_family_cases():
+    """Every (type, mode, EPI) of phasegemm_kernel on 3 x 3 ragged tiles: nk = 1 and odd nk, N % 8 == 4 in the conv modes, both
+    ConvTranspose1d phase shapes (negative dilation, out_row_mul), and the leading-dimension cases."""
+    M, N = 2 * 256 + 37, 2 * 256 + 20                   # conv modes: N % 8 == 4
+    ML, NL = M + 3, N + 4                               # LINEAR: whole 8-row / 8-column staging groups
+    geoms = [("linear-K64", g_linear(ML, NL, 64)), ("linear-K192", g_linear(ML, NL, 192))]
+    geoms += _phase_conv_geoms(M, N, NL, 3)
+    assert M % 3 == 0 and (ML, NL) == (552, 536) and (M, N) == (549, 532)
+    epis = [e for e in family_epilogues() if phase_epi(e) is not None] + x32_epilogues()
+    addr = []
+    for gname, mk in (("linear", lambda **kw: g_linear(ML, NL, 192, **kw)), ("conv1d", lambda **kw: g_conv1d(M, NL, 64, 3, 1, **kw)),
+                      ("conv1d-n532", lambda **kw: g_conv1d(M, N, 64, 3, 1, **kw))):
+        n = N if gname == "conv1d-n532" else NL
+        pad4 = 4 if n % 8 == 0 else 8                   # ldc % 8 == 4: no row of C but the first is 16-byte aligned
+        addr.append((f"lda+ldc/{gname}", mk(lda_pad=16, ldc_pad=pad4),
+                     ["none", "gelu+mask", "lrelu+res16post", "f32out+res16post", "x32+accum"]))
+        addr.append((f"ldc2/{gname}", mk(ldc_pad=pad4 + 4, ldc2_pad=pad4 + 8, c2_skew=True),      # ldc2 % 8 == 4, C2 8-byte aligned
+                     ["dual", "res16post+dual+mask", "x32+accum+dual+mask"]))
+        addr.append((f"ldr/{gname}", mk(lda_pad=8, ldc_pad=pad4), ["stream32-ldr", "stream32-inplace"]))
+    cases = []
+    for dt in DTYPES:
+        for gname, g in geoms:
+            cases += [_case(gname, dt, g, e, PHASE) for e in epis if phase_epi(e, g["N"]) is not None]
+        for gname, g, names in addr:
+            assert (g["ldc2"] % 8 == 4 and g["ldc2"] != g["ldc"]) if g["c2_skew"] else g["ldc"] % 8 == 4
+            cases += [_case(gname, dt, g, e, PHASE) for e in _named(names) if phase_epi(e, g["N"]) is not None]
+    return cases
+
+
+def phase_declined_cases():
+    """The conv-mode launches with N % 8 == 4 and a family 0-6 epilogue: l2s_phasegemm_eligible must decline them even when forced
+    (epilogue_direct16 would leave their last four columns unwritten); the generic tiles serve them."""
+    M, N = 2 * 256 + 37, 2 * 256 + 20
+    return [dict(name=f"{gname}/{e['name']}", dt=dt, mode=g["mode"], uni=g["uni"], family=e["family"], geom=g, epi=e)
+            for dt in DTYPES for gname, g in _phase_conv_geoms(M, N, N, 3) for e in family_epilogues() if e["family"] <= EPI_G16A]
+
+
+WALK_EPIS = ["none", "lrelu+mask", "gelu+mask", "lrelu+res16post", "res16post+dual+mask", "stream32", "x32+accum+dual+mask"]
+
+
+def phase_walk_cases():
+    """7 x 7 tiles under L2S_PHASE_SLOTS=2: slot 0 of XCDs 0-6 walks four tiles, slot 1 three, XCD 7 has none.  The quarter stream,
+    the K-tile parity (odd nk), the accumulators and the conv modes' tap cursor all cross tile boundaries."""
+    ML, NL, M, N = 6 * 256 + 40, 7 * 256 - 8, 6 * 256 + 37, 7 * 256 - 4
+    assert (ML, NL, M, N) == (1576, 1784, 1573, 1788) and M == 11 * 143
+    geoms = [(f"linear-K{K}", g_linear(ML, NL, K)) for K in (64, 128, 192)]
+    for n in (N, NL):                                   # N % 8 == 4: families 7, 8 and X32; N % 8 == 0: 0, 3, 5 and 6
+        geoms += [(f"conv1d-k3-n{n}", g_conv1d(M, n, 64, 3, 1)), (f"conv2d-7x7-n{n}", g_conv2d(M, n, 64, 7, 1)),
+                  (f"convt-k8s4-n{n}", g_convt(11, 143, n, 64, 8, 4))]
+    return [_case("walk/" + gname, dt, g, e, PHASE) for dt in DTYPES for gname, g in geoms for e in _named(WALK_EPIS)
+            if phase_epi(e, g["N"]) is not None and (g["mode"] == MODE_LINEAR or (g["N"] == N) == (e["family"] > EPI_G16A))]
+
+
+def phase_natural_cases():
+    """19 x 14 = 266 tiles on the real grid of 8 x 32 blocks: chunk 34, so slots 0 and 1 of XCDs 0-6 walk two tiles."""
+    M, N = 18 * 256 + 40, 14 * 256 - 8
+    assert (M, N) == (4648, 3576)
+    return [_case(f"natural/linear-K{K}", dt, g_linear(M, N, K), e, PHASE) for dt in DTYPES for K in (64, 192)
+            for e in _named(["none", "stream32"])]
+
+
+def _patch_conv1d(ch, T, k, dil, B=NCLIPS, **kw):
+    return g_conv1d(B * T, ch, ch, k, dil, B=B, **kw)
+
+
+def _patch_conv2d(ch, H, W, nimg, **kw):
+    return g_conv2d(nimg * H * W, ch, ch, H, 1, W=W, **kw)
+
+
+def patch_family_cases(ch):
+    """Every (type, mode, EPI) of patchconv64_kernel<CH> on whole clips / whole images, one to three tiles per clip."""
+    geoms = [("conv1d-k3-T549", _patch_conv1d(ch, 549, 3, 1)),          # three tiles per clip, the last one 37 rows
+             ("conv1d-k11d5-T549", _patch_conv1d(ch, 549, 11, 5)),
+             ("conv1d-k9d8-T300", _patch_conv1d(ch, 300, 9, 8)),        # tap span 64 = the halo limit
+             ("conv1d-k2-T256", _patch_conv1d(ch, 256, 2, 1)),          # ntaps == 2 (offsets 0, +1), T_out == one tile exactly
+             ("conv1d-k7d3-T100", _patch_conv1d(ch, 100, 7, 3)),        # T_out < 256
+             ("conv1d-k3-T7", _patch_conv1d(ch, 7, 3, 1)),
+             ("convt-k8s4", g_convt(NCLIPS, 300, ch, ch, 8, 4)),        # dil -1, out_row_mul 4
+             ("conv2d-18x18", _patch_conv2d(ch, 18, 18, 3)),
+             ("conv2d-16x29", _patch_conv2d(ch, 16, 29, 3)),            # Wi = 29: the widest map the halo admits
+             ("conv2d-40x12", _patch_conv2d(ch, 40, 12, 3))]
+    pads = [("lda+ldc/conv1d", _patch_conv1d(ch, 549, 3, 1, lda_pad=16, ldc_pad=12)),
+            ("lda+ldc/conv2d", _patch_conv2d(ch, 16, 29, 3, lda_pad=16, ldc_pad=12))]
+    pad_epis = _named(["none", "lrelu+mask", "lrelu+res16post", "res16post+dual+mask", "f32out+res16post", "accum16"])
+    kernel = 999000 + ch
+    cases = []
+    for dt in DTYPES:
+        for gname, g in geoms:
+            cases += [_case(gname, dt, g, e, kernel, ch) for e in family_epilogues()]
+        for gname, g in pads:
+            assert g["ldc"] % 8 == 4
+            cases += [_case(gname, dt, g, e, kernel, ch) for e in pad_epis]
+    return cases
+
+
+PATCH_WALK_EPIS = ["relu", "prelu+mask", "res16pre+relu", "res16post+dual+mask",      # paired: next patch issued in the epilogue
+                   "gelu+mask", "stream32", "accum32+dual+mask"]                       # catch-all: barrier, then the next patch
+
+
+def patch_walk_cases(ch):
+    """15 tiles under L2S_PATCH_SLOTS=4: blocks walk 4 / 4 / 4 / 3 tiles, consecutive tiles of a block lie in different clips."""
+    geoms = [("conv1d-k3-T700", _patch_conv1d(ch, 700, 3, 1)), ("conv2d-18x18", _patch_conv2d(ch, 18, 18, 9))]
+    return [_case("walk/" + gname, dt, g, e, 999000 + ch, ch) for dt in DTYPES for gname, g in geoms
+            for e in _named(PATCH_WALK_EPIS)]
+
+
+def patch_natural_cases():
+    """More tiles than the 512 resident blocks of the 64-channel kernel: blocks 0-9 / 0-5 take a second tile."""
+    geoms = [("conv1d-k11d5-T14600", _patch_conv1d(64, 14600, 11, 5, B=9), "res16post+dual+mask"),
+             ("conv2d-22x22", _patch_conv2d(64, 22, 22, 230), "res16pre+relu")]
+    return [_case("natural/" + gname, dt, g, _named([en])[0], PATCH64, 64) for dt in DTYPES for gname, g, en in geoms]
+
+
+def special_cases(part, kernel):
+    if part == "phase-families":
+        return phase_family_cases()
+    if part == "phase-walk":
+        return phase_walk_cases()
+    if part == "phase-natural":
+        return phase_natural_cases()
+    ch = kernel - 999000
+    if part == "patch-families":
+        return patch_family_cases(ch)
+    if part == "patch-walk":
+        return patch_walk_cases(ch)
+    if part == "patch-natural":
+        return patch_natural_cases()
+    raise ValueError(part)
+
+
 def cases_of(part, tile):
+    if part in PART_ENV:
+        assert tile in PART_KERNELS[part], (part, tile)
+        return special_cases(part, tile)
     if part == "families":
         return family_cases(tile)
     if part == "schedule":
@@ -290,7 +562,7 @@ def descriptors(case):
     if g["kind"] == "conv1d":
         d.update(T_out=g["T"], T_in=g["T"], stride=1, dil=g["dil"], off=g["off"])
     elif g["kind"] == "conv2d":
-        d.update(Ho=g["Ho"], Wo=g["Ho"], Hi=g["H"], Wi=g["H"], KW=3, pad=1, stride=g["stride"])
+        d.update(Ho=g["Ho"], Wo=g.get("Wo", g["Ho"]), Hi=g["H"], Wi=g.get("Wi", g["H"]), KW=3, pad=1, stride=g["stride"])
     elif g["kind"] == "convt":
         return [dict(d, T_out=g["T"], T_in=g["T"], stride=1, dil=-1, off=ph["off"], ntaps=ph["ntaps"], out_row_add=ph["r"],
                      w_gstride=0) for ph in g["phases"]]

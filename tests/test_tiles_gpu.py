@@ -18,7 +18,9 @@ def test_forced_tile(tile):
 
 
 def test_phase_staggered_kernel_forced():
-    """csrc/phasegemm.hip on every family / ragged shape, whatever the selection heuristic would do.  (The four-wave
+    """csrc/phasegemm.hip on every family / ragged shape, whatever the selection heuristic would do, at one output tile per block:
+    blocks that walk several tiles, and every (type, mode, epilogue) instantiation against fp64, are the phase-* parts of
+    tests/test_tapgemm_matrix_gpu.py.  (The four-wave
     128x128-wave-tile alternative, csrc/widegemm_kernel.h, is no longer part of the product library: build it with
     `make -C lip2speech_unit_amd/csrc WIDE=1` into a variant and run tools/check_phasegemm.py with L2S_WIDEGEMM=1 against it.)"""
     env = dict(os.environ, L2S_PHASEGEMM="2")

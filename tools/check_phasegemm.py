@@ -1,7 +1,9 @@
 #!/usr/bin/env python3
 """Checks the phase-staggered 256x256 kernel (csrc/phasegemm.hip, forced with L2S_PHASEGEMM=2) against torch fp32:
-every epilogue family it is built for, ragged M / N tails, one to many tiles per block, repeated runs (the kernel's
-LDS hand-over is ordered by counted vmcnt + barriers: a race would show as rare wrong tiles).
+every epilogue family it is built for, ragged M / N tails, repeated runs (the kernel's LDS hand-over is ordered by counted
+vmcnt + barriers: a race would show as rare wrong tiles).  Every shape here stays at ONE output tile per block (at most 252 tiles
+on the grid of 256 blocks): blocks that walk several tiles are the phase-walk / phase-natural parts of
+tools/check_tapgemm_matrix.py (tests/test_tapgemm_matrix_gpu.py).
 Used by tests/test_tiles_gpu.py."""
 import ctypes, os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))

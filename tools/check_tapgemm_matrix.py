@@ -1,8 +1,15 @@
 #!/usr/bin/env python3
-"""Runs one part of the tap-GEMM instantiation matrix (tests/_tapgemm_cases.py) on the tile forced by L2S_FORCE_TILE.
+"""Runs one part of the tap-GEMM instantiation matrix (tests/_tapgemm_cases.py): a generic tile forced by L2S_FORCE_TILE,
 
     L2S_FORCE_TILE=<tile> L2S_PHASEGEMM=0 L2S_NO_PATCHCONV=1 check_tapgemm_matrix.py families|schedule|band
 
+or the phase-staggered kernel (256256) / the LDS-patch kernel (999064, 999128) under the switches of tc.PART_ENV[part],
+
+    L2S_PHASEGEMM=2 [L2S_PHASE_SLOTS=2] check_tapgemm_matrix.py phase-families|phase-walk|phase-natural 256256
+    L2S_PATCH_MIN_M=1 L2S_PHASEGEMM=0 [L2S_PATCH_SLOTS=4] check_tapgemm_matrix.py patch-families|patch-walk|patch-natural 999064
+
+With --route in front of the part only the dispatch is checked (every launch of every case is routed to the kernel and the
+epilogue family the case claims): no device needed.
 The library reads these switches once per process, hence one child process per (tile, part): tests/test_tapgemm_matrix_gpu.py.
 Every case runs on operands that are views into NaN-filled device buffers (guard rows around A / C / C2 / R, NaN in the padding
 columns of the leading dimensions, a NaN guard behind W) and is checked for: no NaN inside the written window, every byte outside
@@ -29,6 +36,7 @@ from tests import _tapgemm_cases as tc  # noqa: E402
 TOL = {"f16": 2e-3, "bf16": 1.5e-2}          # (a): TOL of tests/test_tapgemm_gpu.py
 U16 = {"f16": 2.0 ** -11, "bf16": 2.0 ** -8}
 FU, FK, ABS = 1.5, 4.0, 2.0 ** -24           # (b): margins over the half-ulp and gamma_K bounds; f16 subnormal step
+GENERIC_PARTS = ("families", "schedule", "band")   # on a forced generic tile; every other part names its kernel and switches
 GUARD = 4                                    # guard rows (keeps every window 16-byte aligned: leading dimensions are 4 | ld)
 NAN = float("nan")
 f64 = torch.float64
@@ -58,10 +66,15 @@ def oracle(g, A, W):
         elif g["kind"] == "conv1d":
             x = a.reshape(g["B"], g["T"], Cin).permute(0, 2, 1)
             wc = w.reshape(N, g["k"], Cin).permute(0, 2, 1)
-            y = F.conv1d(x, wc, None, 1, -g["off"], g["dil"]).permute(0, 2, 1).reshape(-1, N)[: g["M"]]
+            right = (g["k"] - 1) * g["dil"] + g["off"]
+            if right != -g["off"]:                                   # even k: taps off .. off + (k - 1) dil around frame t
+                x, pad = F.pad(x, (-g["off"], right)), 0
+            else:
+                pad = -g["off"]
+            y = F.conv1d(x, wc, None, 1, pad, g["dil"]).permute(0, 2, 1).reshape(-1, N)[: g["M"]]
         elif g["kind"] == "conv2d":
             H = g["H"]
-            x = a.reshape(g["nimg"], H, H, Cin).permute(0, 3, 1, 2)
+            x = a.reshape(g["nimg"], H, g.get("Wi", H), Cin).permute(0, 3, 1, 2)
             wc = w.reshape(N, 3, 3, Cin).permute(0, 3, 1, 2)
             y = F.conv2d(x, wc, None, g["stride"], 1).permute(0, 2, 3, 1).reshape(-1, N)[: g["M"]]
         else:  # convt: W holds the ConvTranspose1d weight [Cin, N, k]
@@ -80,7 +93,7 @@ def operands(case):
     gen = torch.Generator().manual_seed(1000 * g["M"] + 10 * g["N"] + g["Cin"] + len(dt))
     G, N, Cin = g["groups"], g["N"], g["Cin"]
     rows_in = {"linear": g["M"], "conv1d": g.get("B", 0) * g.get("T", 0), "convt": g.get("B", 0) * g.get("T", 0),
-               "conv2d": g.get("nimg", 0) * g.get("H", 0) ** 2}[g["kind"]]
+               "conv2d": g.get("nimg", 0) * g.get("H", 0) * g.get("Wi", g.get("H", 0))}[g["kind"]]
     A = rnd(torch.randn(rows_in, g["a_cols"], generator=gen, dtype=f64), dt)
     if g["kind"] == "convt":
         fan = Cin * g["k"] / g["s"]
@@ -177,7 +190,7 @@ class Report:
         self.tile, self.fail, self.worst = tile, [], {}
 
     def ratio(self, case, crit, r):
-        k = (case["dt"], case["family"], crit)
+        k = (case["inst"] if "inst" in case else (case["dt"], case["family"]), crit)
         self.worst[k] = max(self.worst.get(k, 0.0), r)
 
     def bad(self, case, why):
@@ -293,13 +306,44 @@ def run_case(case, lib, tile, rep):
                               f"ref {rf.reshape(-1)[i].item():.9g}, {(q > 1).sum().item()} elements over)")
 
 
+def route(part, kernel, lib):
+    """Dispatch only: how many launches of the part's cases are NOT routed to the kernel / epilogue family they claim."""
+    bad = n = 0
+    for case in tc.cases_of(part, kernel):
+        for d in tc.descriptors(case):
+            gd = _lib.GemmDesc(**d)
+            got = (lib.l2s_tapgemm_variant(ctypes.byref(gd)), lib.l2s_tapgemm_epilogue_family(ctypes.byref(gd)))
+            n += 1
+            if got != (kernel, case["family"]):
+                bad += 1
+                print(f"ROUTE {part} {case['dt']} {case['name']}: variant {got[0]} family {got[1]}")
+    print(f"routed {n - bad} of {n} launches of {part} to {kernel}")
+    if part == "phase-families":            # what the kernel must decline although forced: served by a generic tile
+        for case in tc.phase_declined_cases():
+            for d in tc.descriptors(case):
+                var = lib.l2s_tapgemm_variant(ctypes.byref(_lib.GemmDesc(**d)))
+                if var not in tc.TILES:
+                    bad += 1
+                    print(f"ROUTE {part} {case['dt']} {case['name']}: variant {var}, a generic tile expected")
+    return bad
+
+
 def main():
-    part = sys.argv[1]
-    tile = int(os.environ["L2S_FORCE_TILE"])
-    assert os.environ.get("L2S_PHASEGEMM") == "0" and os.environ.get("L2S_NO_PATCHCONV") == "1", "generic kernel only"
-    if part == "band":
-        assert os.environ.get("L2S_BAND") == str(tc.BAND)
+    args = sys.argv[1:]
+    route_only = args[0] == "--route"
+    part = args[1] if route_only else args[0]
+    if part not in GENERIC_PARTS:
+        tile = int(args[-1])
+        for name in tc.SWITCHES:            # the kernel under test, its grid and its threshold: exactly the part's switches
+            assert os.environ.get(name) == tc.PART_ENV[part].get(name), (name, os.environ.get(name))
+    else:
+        tile = int(os.environ["L2S_FORCE_TILE"])
+        assert os.environ.get("L2S_PHASEGEMM") == "0" and os.environ.get("L2S_NO_PATCHCONV") == "1", "generic kernel only"
+        if part == "band":
+            assert os.environ.get("L2S_BAND") == str(tc.BAND)
     lib = _lib.load()
+    if route_only:
+        sys.exit(1 if route(part, tile, lib) else 0)
     rep = Report(tile)
     t0 = time.time()
     cases = tc.cases_of(part, tile)
@@ -307,11 +351,16 @@ def main():
         run_case(case, lib, tile, rep)
     dt_s = time.time() - t0
     print(f"tile {tile} part {part}: {len(cases)} cases, {len(rep.fail)} failures, {dt_s:.1f} s")
-    print("worst err/bound   " + "  ".join(f"fam{f}" for f in range(10)))
-    for dt in tc.DTYPES:
-        for crit in "ab":
-            cells = [rep.worst.get((dt, f, crit)) for f in range(10)]
-            print(f"RATIO {tile} {part} {dt:4s} ({crit}) " + " ".join("    -" if c is None else f"{c:5.3f}" for c in cells))
+    if part not in GENERIC_PARTS:                 # one line per instantiation: (type, mode, EPI) / (type, mode, CH, EPI)
+        for inst in sorted({k for k, _ in rep.worst}):
+            a, b = rep.worst.get((inst, "a")), rep.worst.get((inst, "b"))
+            print(f"RATIO {tile} {part} " + " ".join(str(x) for x in inst) + f" (a) {a:5.3f} (b) " + ("    -" if b is None else f"{b:5.3f}"))
+    else:
+        print("worst err/bound   " + "  ".join(f"fam{f}" for f in range(10)))
+        for dt in tc.DTYPES:
+            for crit in "ab":
+                cells = [rep.worst.get(((dt, f), crit)) for f in range(10)]
+                print(f"RATIO {tile} {part} {dt:4s} ({crit}) " + " ".join("    -" if c is None else f"{c:5.3f}" for c in cells))
     for line in rep.fail:
         print(line)
     sys.exit(1 if rep.fail else 0)
