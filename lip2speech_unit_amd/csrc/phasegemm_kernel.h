@@ -23,6 +23,34 @@
 // (rows 0-63, cols 0-31) -> (0-63, 32-63) -> (64-127, 32-63) -> (64-127, 0-31): 8+4, 4, 8, 0 fragment reads.
 // Persistent blocks (the quarter stream runs across the block's output tiles), XCD-aware banded tile order and
 // epilogue_fast16 are shared with tapgemm_kernel.h.
+//
+// TILE BOUNDARY: the rows are levelled for the epilogue and staggered again behind it.  E = the early row (waves 0-3), L = the late
+// row (waves 4-7); A(p) / B(p) = the first / second barrier of phase p, p counting the block's phases across its tiles.  Inside a
+// tile the rows' barriers pair as E.A(p) = L.B(p-1), E.B(p) = L.A(p).  An epilogue holds no barrier, so with nothing more the two
+// rows' epilogues SERIALISE: L sits in B(z) of the tile's last phase z until E arrives at A(z+1) - behind E's epilogue - and then E
+// sits in B(z+1) until L arrives at A(z+1) - behind L's epilogue: 2 x epilogue per tile with one wave of every SIMD parked.
+// With p_level(EPI) each row executes one extra barrier per tile, X in front of E's epilogue and Y behind L's:
+//     E:  A(z) B(z)  X   epilogue       A(z+1) B(z+1) ...
+//     L:       A(z) B(z)  epilogue   Y        A(z+1) B(z+1) ...        pairs: E.X = L.B(z), E.A(z+1) = L.Y, E.B(z+1) = L.A(z+1)
+// so both rows run their epilogues side by side behind one common barrier, and Y puts L one barrier behind again exactly as the
+// prologue's `if (wr == 1) s_barrier` does.  Y is not executed behind the block's LAST tile.
+// Barrier count per block, T = my_n >= 1 tiles of nk_1 .. nk_T K-tiles (any values; in the K-block-table mode they differ from tile
+// to tile, but a tile's count is one scalar for the whole block), P = 4 (nk_1 + .. + nk_T) phases:
+//     E: 1 (prologue) + 2 P + T (X)            L: 2 (prologue + stagger) + 2 P + (T - 1) (Y)            both 2 P + T + 1
+// (T = 1: 2 P + 2 each, no Y at all; T = 2: 2 P + 3; ...).  Every tile adds 8 nk_t + 1 to both rows, so the pairing above repeats
+// at every boundary whatever the K-tile counts are.  Without levelling (-DL2S_NO_LEVEL, or an EPI p_level() excludes) E executes
+// 1 + 2 P and L 2 + 2 P barriers: L's last one is released by E's waves ending.
+// Hazards at the boundary (program order of reads, stagings and waits per wave is that of the K loop, the stream does not stop):
+//   RAW  phase z+1 reads what every wave's vmcnt(8) of phase z retired, and that wait stands in front of the wave's own A(z).
+//        E reads for z+1 behind X = L.B(z), which L passes after its A(z); L reads for z+1 behind Y = E.A(z+1), which E passes after
+//        its A(z): every staged quarter is read at least one common barrier (here: two) after every wave's retiring wait.
+//   WAR  the staging of phase p overwrites a quarter last read in phase p-2 or earlier, and a wave's reads of phase p are complete
+//        (lds_wait) before it arrives at its B(p).  E stages for z+1 behind X = L.B(z) and for z+2 behind B(z+1) = L.A(z+1) > L.B(z):
+//        L's reads of z-1 and z are complete.  L stages for z+1 behind Y = E.A(z+1) and for z+2 behind B(z+1) = E.A(z+2): E's reads of
+//        z-1 and z were complete at E.B(z).  Every quarter is restaged at least two phases and one more barrier than inside a tile
+//        after its last read by either row.
+//   The epilogues' scratch is wave-private and lies behind the ring; their loads and stores are younger than the six quarters in
+//   flight, so the next phase's vmcnt(8) retires at least what it retired before.
 #pragma once
 #include "tapgemm_common.h"
 #include <cstdlib>
@@ -39,8 +67,18 @@ constexpr bool p_generic(int epi) { return epi == L2S_EPI_G16A || epi == L2S_EPI
 constexpr int p_scr_b(int epi) { return p_generic(epi) ? 16 * 64 * 4 : 16 * (4 * 32 + 16); }
 constexpr int p_smem(int epi) { return 8 * Q_B + 8 * p_scr_b(epi); }   // 128 KB + 18 KB, or exactly 160 KB
 
+// Both wave rows of a tile run their epilogues side by side (header: TILE BOUNDARY).  A compile-time property of the epilogue family:
+// every family measured faster or equal levelled, so all are; -DL2S_NO_LEVEL (A/B switch of the diagnostic
+// builds) restores the schedule in which the rows' epilogues follow each other.
+#ifdef L2S_NO_LEVEL
+constexpr bool p_level(int) { return false; }
+#else
+constexpr bool p_level(int) { return true; }
+#endif
+
 // Diagnostic build (-DL2S_PHASE_STAMPS, tools/phase_stamps.py): waves 0 and 7 of every block accumulate s_memtime deltas of
-// [0] K loops, [1] epilogues, [2] the wait at the first barrier after an epilogue (the block's slowest wave), and count tiles.
+// [0] K loops, [1] epilogues, [2] the first K-tile after an epilogue (without levelling it includes the wait for the other row's
+// epilogue), [3] the two levelling barriers (X in wave 0, Y in wave 7), and count tiles.
 #ifdef L2S_PHASE_STAMPS
 __device__ unsigned long long* g_phase_stamps = nullptr;
 #define PHSTAMP(i) { const unsigned long long now_ = __builtin_amdgcn_s_memtime(); ph_acc[i] += now_ - ph_last; ph_last = now_; }
@@ -433,6 +471,14 @@ __global__ __launch_bounds__(512) void phasegemm_kernel(const l2s_gemm_desc p, c
       par ^= 1;
     }
     PHSTAMP(0)
+    if constexpr (p_level(EPI)) {                          // X: pairs with the late row's closing barrier of the tile's last phase
+      if (wr == 0) {
+        asm volatile("" ::: "memory");
+        __builtin_amdgcn_s_barrier();
+        asm volatile("" ::: "memory");
+      }
+      PHSTAMP(3)
+    }
     int m0, n0, grp;                                       // grp: column block / bias row of this problem (the epilogues' group argument)
     tile_coords(ti, m0, n0, grp);
     const uint32_t scr = lds_base + 8 * Q_B + (uint32_t)wave * p_scr_b(EPI);   // wave-private, behind the quarter slots
@@ -456,6 +502,14 @@ __global__ __launch_bounds__(512) void phasegemm_kernel(const l2s_gemm_desc p, c
 #pragma unroll
       for (int j = 0; j < NI; ++j) acc[i][j] = f32x4_t{0.f, 0.f, 0.f, 0.f};
     PHSTAMP(1)
+    if constexpr (p_level(EPI)) {                          // Y: the late row one barrier behind again; pairs with the early row's A
+      if (wr == 1 && ti + 1 < my_n) {                      // of the next tile's first phase.  Not behind the block's last tile.
+        asm volatile("" ::: "memory");
+        __builtin_amdgcn_s_barrier();
+        asm volatile("" ::: "memory");
+      }
+      PHSTAMP(3)
+    }
   }
   wait_vmcnt<0>();   // no LDS-DMA (the trailing dummies) may outlive the block's LDS allocation
 #ifdef L2S_PHASE_STAMPS
@@ -465,6 +519,7 @@ __global__ __launch_bounds__(512) void phasegemm_kernel(const l2s_gemm_desc p, c
     o[3] = (unsigned long long)my_n;
     o[4] = __builtin_amdgcn_s_memtime() - ph_t0;
     o[5] = (unsigned long long)nk;
+    o[6] = ph_acc[3];
   }
 #endif
 }

@@ -2,9 +2,16 @@
 """Where a block of the phase-staggered GEMM spends its time (diagnostic build, -DL2S_PHASE_STAMPS):
   tools/build_variant.sh stamps -DL2S_PHASE_STAMPS phasegemm_inst:e0_m0
   L2S_LIB_PATH=build_ab/stamps/liblip2speech_hip.so L2S_PHASEGEMM=2 python tools/phase_stamps.py [clips=640]
-Per shape: K loop / epilogue / first-K-tile-after-epilogue (includes the wait for the block's slowest wave) per tile, for wave 0
-(lower wave row) and wave 7 (upper row, one barrier behind), averaged over blocks; s_memtime ticks are converted with the
-launch's HIP-event time."""
+Per shape and per tile, for wave 0 (lower wave row, early) and wave 7 (upper row, one barrier behind), averaged over blocks:
+  K loop        K-tiles 2 .. nk of the tile (stamp 0)
+  first K-tile  the tile's first K-tile (stamp 2); in a build without levelling (-DL2S_NO_LEVEL, or a commit before it) wave 0 waits
+                here, in the closing barrier of phase 0, for the late row's epilogue
+  level         the two levelling barriers (stamp 3): X in front of wave 0's epilogue, Y behind wave 7's; 0 without levelling, where
+                wave 7 spends the early row's epilogue inside its K loop column (the closing barrier of the last phase)
+  epilogue      the epilogue itself (stamp 1)
+  outside       everything that is not K loop at the steady rate: first K-tile + level + epilogue - one steady K-tile
+                (K loop / (nk - 1)); ~ 2 epilogues where the rows' epilogues follow each other, ~ one (E') where they run side by side
+s_memtime ticks are converted with the launch's HIP-event time."""
 import ctypes, os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
@@ -49,7 +56,12 @@ for name, M, N, K, kind in SHAPES:
     for wv, label in ((0, "wave 0"), (1, "wave 7")):
         n = st[:, wv, 3]
         kl, ep, fw = (st[:, wv, i] / n * tick_us for i in range(3))
+        lv = st[:, wv, 6] / n * tick_us
+        nk = st[0, 0, 5].item()
+        steady = kl / (nk - 1) if nk > 1 else torch.zeros_like(kl)
+        outside = fw + lv + ep - steady
         tot = st[:, wv, 4] * tick_us
-        print(f"   {label}: per tile  K loop {kl.mean():6.2f} us (+ first K-tile after an epilogue {fw.mean():5.2f})  epilogue {ep.mean():6.2f} us "
-              f"[min {ep.min():.2f} max {ep.max():.2f}]  block total {tot.mean():7.1f} us (max {tot.max():.1f})")
+        print(f"   {label}: per tile  K loop {kl.mean():6.2f} us (K-tile {steady.mean():5.2f})  first K-tile {fw.mean():5.2f}  level {lv.mean():5.2f}  "
+              f"epilogue {ep.mean():6.2f} us [min {ep.min():.2f} max {ep.max():.2f}]  outside the K loop {outside.mean():6.2f} us  "
+              f"block total {tot.mean():7.1f} us (max {tot.max():.1f})")
     del a, w
