@@ -193,6 +193,17 @@ int l2s_avgpool_hw(const void* x, void* y, int N, int HW, int C, int dtype, void
 int l2s_layernorm(const void* x, int x_is_f32, int ldx, const float* gamma, const float* beta, float eps,
                   void* y, int y_is_f32, int ldy, void* y2, int ldy2, int M, int C, int zero_prefix,
                   const int32_t* lens, int len_mul, int mask_T, int dtype, void* stream);
+/* Host-only queries (nothing launched, no pointer dereferenced; pointers count for null / alignment only): the kernel
+ * instantiation the launcher runs for these arguments, or the error code the launch would answer.  L2S_SEQ_VARIANT_F32 for an
+ * fp32 launch.
+ * l2s_layernorm_variant: L2S_LN_GENERIC + 2 x_is_f32 + y_is_f32 = the one-row-per-wave kernel (any C, zero_prefix, y2);
+ * 512 + y_is_f32 / 1024 + y_is_f32 = the rows kernel of that width (fp32 x, no y2, no zero_prefix; a 16-bit y needs 16-byte
+ * alignment and ldy % 8 == 0, else the generic kernel runs). */
+#define L2S_SEQ_VARIANT_F32 2000
+#define L2S_LN_GENERIC 10
+int l2s_layernorm_variant(const void* x, int x_is_f32, int ldx, const float* gamma, const float* beta, const void* y, int y_is_f32,
+                          int ldy, const void* y2, int ldy2, int M, int C, int zero_prefix, const int32_t* lens, int len_mul,
+                          int mask_T, int dtype);
 
 /*
  * Fused multi-head self-attention with key-padding mask, fp32 online softmax.
@@ -206,6 +217,11 @@ int l2s_layernorm(const void* x, int x_is_f32, int ldx, const float* gamma, cons
 int l2s_attention(const void* qkv, int ldq, void* out, int ldo, const void* pos, int ldp,
                   const float* bias_u, const float* bias_v, const int32_t* lens, int len_mul,
                   int B, int T, int H, int dtype, void* stream);
+/* l2s_attention_variant (host-only, as l2s_layernorm_variant): 64 + rel / 128 + rel = the tiled kernel on 64- / 128-row query
+ * blocks, L2S_ATTN_RESIDENT + rel = the sequence-resident kernel; rel = 1 with a position table. */
+#define L2S_ATTN_RESIDENT 1000
+int l2s_attention_variant(const void* qkv, int ldq, const void* out, int ldo, const void* pos, int ldp, const float* bias_u,
+                          const float* bias_v, const int32_t* lens, int len_mul, int B, int T, int H, int dtype);
 
 /*
  * Conformer conv-module core: GLU(dim=C) -> depthwise Conv1d(k, pad (k-1)/2, groups=C) -> BatchNorm1d(eval, folded)
@@ -214,6 +230,9 @@ int l2s_attention(const void* qkv, int ldq, void* out, int ldo, const void* pos,
  */
 int l2s_glu_dwconv_swish(const void* x, const float* w, const float* bias, void* y, const int32_t* lens,
                          int len_mul, int B, int T, int C, int k, int dtype, void* stream);
+/* l2s_glu_dwconv_tile (host-only): the time steps per block the launcher picks, 100 or 128 (L2S_SEQ_VARIANT_F32 for fp32), or
+ * the launch's error code for these shapes. */
+int l2s_glu_dwconv_tile(int B, int T, int C, int k, int dtype);
 
 /*
  * Greedy unit decode == hypothesis 0 of the reference beam search (multi_target_lip2speech/sequence_generator.py:235-494):

@@ -14,6 +14,7 @@ ACT_NONE, ACT_RELU, ACT_GELU, ACT_SWISH, ACT_PRELU, ACT_LRELU, ACT_TANH = range(
 F_RES_PRE, F_RES_POST, F_ACCUM, F_DUAL, F_MASK, F_OUT_F32, F_RES_F32 = (1 << i for i in range(7))
 MODE_LINEAR, MODE_CONV1D, MODE_CONV2D = 0, 1, 2
 ABI_VERSION = 16
+SEQ_VARIANT_F32, LN_GENERIC, ATTN_RESIDENT = 2000, 10, 1000   # l2s_layernorm_variant / l2s_attention_variant / l2s_glu_dwconv_tile
 
 _ERR = {-1: "L2S_EINVAL", -2: "L2S_ESHAPE", -3: "L2S_EALIGN", -4: "L2S_EUNSUPPORTED"}
 
@@ -75,6 +76,9 @@ SIGNATURES = {
     "l2s_maxpool2d_3x3s2": ([_vp, _vp, _i, _i, _i, _i, _i, _vp], _i),
     "l2s_avgpool_hw": ([_vp, _vp, _i, _i, _i, _i, _vp], _i),
     "l2s_layernorm": ([_vp, _i, _i, _vp, _vp, _f, _vp, _i, _i, _vp, _i, _i, _i, _i, _vp, _i, _i, _i, _vp], _i),
+    "l2s_layernorm_variant": ([_vp, _i, _i, _vp, _vp, _vp, _i, _i, _vp, _i, _i, _i, _i, _vp, _i, _i, _i], _i),
+    "l2s_attention_variant": ([_vp, _i, _vp, _i, _vp, _i, _vp, _vp, _vp, _i, _i, _i, _i, _i], _i),
+    "l2s_glu_dwconv_tile": ([_i, _i, _i, _i, _i], _i),
     "l2s_attention": ([_vp, _i, _vp, _i, _vp, _i, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp], _i),
     "l2s_glu_dwconv_swish": ([_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp], _i),
     "l2s_greedy_decode": ([_vp, _i, _vp, _i, _i, _i, _i, _f, _f, _vp, _vp, _vp, _vp], _i),

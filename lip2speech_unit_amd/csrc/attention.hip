@@ -240,7 +240,7 @@ __global__ __launch_bounds__(QB * 4) void attention_kernel(const uint16_t* __res
 // Blocks b and b+8 share an XCD and H = 8, so every block of an XCD works on the same head (its table stays in that L2).
 constexpr int RES_MAX_T = 208;   // 13 compute waves + 3 loader waves
 constexpr int RES_FRONT = 16;   // zero rows in front of the position image (query rows past T reach "before" the table)
-constexpr int RES_MAXC = 10;    // K/V 16-byte chunk pairs a loader lane holds: 224 rows x 8 chunks / (3 waves x 64 lanes)
+constexpr int RES_MAXC = 10;    // K/V 16-byte chunk pairs a loader lane holds: 224 rows (tp32 of 208) x 8 chunks / (3 waves x 64 lanes), rounded up
 
 struct ResLayout {
   int tp16, tp32, prows, k_off, v_off, p_off, bias_off, bd_off, bytes;
@@ -528,29 +528,49 @@ __global__ __launch_bounds__(1024) void attention_resident_kernel(const uint16_t
 int l2s_f32_attention(const void* qkv, int ldq, void* out, int ldo, const void* pos, int ldp, const float* bias_u, const float* bias_v,
                       const int32_t* lens, int len_mul, int B, int T, int H, hipStream_t st);
 
-extern "C" int l2s_attention(const void* qkv, int ldq, void* out, int ldo, const void* pos, int ldp,
-                             const float* bias_u, const float* bias_v, const int32_t* lens, int len_mul, int B, int T,
-                             int H, int dtype, void* stream) {
+// Which kernel a launch runs on (or the error the launch answers): the one place the dispatch is decided, shared by
+// l2s_attention and the host-only query l2s_attention_variant.  No pointer is dereferenced.
+static int attention_select(const void* qkv, int ldq, const void* out, int ldo, const void* pos, int ldp, const float* bias_u,
+                            const float* bias_v, const int32_t* lens, int len_mul, int B, int T, int H, int dtype) {
   if (!qkv || !out) return L2S_EINVAL;
   if (B <= 0 || T <= 0 || H <= 0) return L2S_ESHAPE;
   if ((ldq & 7) || (ldo & 3) || ((uintptr_t)qkv & 15) || ((uintptr_t)out & 7)) return L2S_EALIGN;
   if (ldq < 3 * H * D || ldo < H * D) return L2S_ESHAPE;
   if (pos && (!bias_u || !bias_v || (ldp & 7) || ldp < H * D || ((uintptr_t)pos & 15))) return L2S_EINVAL;
   if (lens && len_mul <= 0) return L2S_EINVAL;
-  hipStream_t st = (hipStream_t)stream;
-  if (dtype == L2S_F32) {   // qkv, pos and out are fp32; any T (no resident form)
-    if ((uintptr_t)out & 15) return L2S_EALIGN;
-    return l2s_f32_attention(qkv, ldq, out, ldo, pos, ldp, bias_u, bias_v, lens, len_mul, B, T, H, st);
-  }
-  const uint16_t* q = (const uint16_t*)qkv;
-  uint16_t* o = (uint16_t*)out;
-  const uint16_t* pp = (const uint16_t*)pos;
+  if (dtype == L2S_F32) return ((uintptr_t)out & 15) ? L2S_EALIGN : L2S_SEQ_VARIANT_F32;  // any T (no resident form)
+  if (dtype != L2S_F16 && dtype != L2S_BF16) return L2S_EINVAL;
+  const int rel = pos ? 1 : 0;
   // short rel-pos clips: the sequence-resident kernel (whole K / V / position table in LDS, persistent block per head)
   static const int resident_on = [] { const char* e = getenv("L2S_ATTN_RESIDENT"); return e ? atoi(e) : 1; }();  // A/B switch
   // (the plain fairseq MultiheadAttention launches can take the same kernel without the position terms: measured 158 vs 152 us
   // at T = 100, 640 clips - the tiled kernel already runs them at the rate its loads arrive - so that stays an A/B switch, off)
   static const int plain_on = [] { const char* e = getenv("L2S_ATTN_RESIDENT_PLAIN"); return e ? atoi(e) : 0; }();
-  if (resident_on && (pos || plain_on) && T <= RES_MAX_T && H <= 256) {
+  if (resident_on && (pos || plain_on) && T <= RES_MAX_T && H <= 256 && ResLayout(T, pos != nullptr).bytes <= 160 * 1024)
+    return L2S_ATTN_RESIDENT + rel;
+  // 128-row blocks when they do not add padded query rows over 64-row blocks (or T is long enough not to care)
+  static const int force_qb = [] { const char* e = getenv("L2S_ATTN_QB"); return e ? atoi(e) : 0; }();  // 64 / 128: tools
+  const bool big = force_qb ? force_qb == 128 : ((((T + 63) / 64) % 2 == 0) || T >= 512);
+  return (big ? 128 : 64) + rel;
+}
+
+extern "C" int l2s_attention_variant(const void* qkv, int ldq, const void* out, int ldo, const void* pos, int ldp, const float* bias_u,
+                                     const float* bias_v, const int32_t* lens, int len_mul, int B, int T, int H, int dtype) {
+  return attention_select(qkv, ldq, out, ldo, pos, ldp, bias_u, bias_v, lens, len_mul, B, T, H, dtype);
+}
+
+extern "C" int l2s_attention(const void* qkv, int ldq, void* out, int ldo, const void* pos, int ldp,
+                             const float* bias_u, const float* bias_v, const int32_t* lens, int len_mul, int B, int T,
+                             int H, int dtype, void* stream) {
+  const int var = attention_select(qkv, ldq, out, ldo, pos, ldp, bias_u, bias_v, lens, len_mul, B, T, H, dtype);
+  if (var < 0) return var;
+  hipStream_t st = (hipStream_t)stream;
+  if (var == L2S_SEQ_VARIANT_F32)   // qkv, pos and out are fp32
+    return l2s_f32_attention(qkv, ldq, out, ldo, pos, ldp, bias_u, bias_v, lens, len_mul, B, T, H, st);
+  const uint16_t* q = (const uint16_t*)qkv;
+  uint16_t* o = (uint16_t*)out;
+  const uint16_t* pp = (const uint16_t*)pos;
+  if (var >= L2S_ATTN_RESIDENT) {
     const ResLayout L(T, pos != nullptr);
     int nslots = 256 / H;
     if (nslots < 1) nslots = 1;
@@ -564,19 +584,14 @@ extern "C" int l2s_attention(const void* qkv, int ldq, void* out, int ldo, const
                          len_mul, T, H, B);
       return L2S_OK;
     };
-    if (L.bytes <= 160 * 1024) {
-      int rc;
-      if (dtype == L2S_F16) rc = pos ? go_res(ElemF16{}, std::true_type{}) : go_res(ElemF16{}, std::false_type{});
-      else if (dtype == L2S_BF16) rc = pos ? go_res(ElemBF16{}, std::true_type{}) : go_res(ElemBF16{}, std::false_type{});
-      else return L2S_EINVAL;
-      if (rc != L2S_OK) return rc;
-      L2S_CHECK_LAUNCH();
-      return L2S_OK;
-    }
+    int rc;
+    if (dtype == L2S_F16) rc = pos ? go_res(ElemF16{}, std::true_type{}) : go_res(ElemF16{}, std::false_type{});
+    else rc = pos ? go_res(ElemBF16{}, std::true_type{}) : go_res(ElemBF16{}, std::false_type{});
+    if (rc != L2S_OK) return rc;
+    L2S_CHECK_LAUNCH();
+    return L2S_OK;
   }
-  // 128-row blocks when they do not add padded query rows over 64-row blocks (or T is long enough not to care)
-  static const int force_qb = [] { const char* e = getenv("L2S_ATTN_QB"); return e ? atoi(e) : 0; }();  // 64 / 128: tools
-  const bool big = force_qb ? force_qb == 128 : ((((T + 63) / 64) % 2 == 0) || T >= 512);
+  const bool big = (var & ~1) == 128;
   auto go = [&](auto et, auto rel, auto qb) -> int {
     using ET = decltype(et);
     constexpr bool R = decltype(rel)::value;
@@ -594,8 +609,7 @@ extern "C" int l2s_attention(const void* qkv, int ldq, void* out, int ldo, const
   };
   int rc;
   if (dtype == L2S_F16) rc = pos ? go_q(ElemF16{}, std::true_type{}) : go_q(ElemF16{}, std::false_type{});
-  else if (dtype == L2S_BF16) rc = pos ? go_q(ElemBF16{}, std::true_type{}) : go_q(ElemBF16{}, std::false_type{});
-  else return L2S_EINVAL;
+  else rc = pos ? go_q(ElemBF16{}, std::true_type{}) : go_q(ElemBF16{}, std::false_type{});
   if (rc != L2S_OK) return rc;
   L2S_CHECK_LAUNCH();
   return L2S_OK;

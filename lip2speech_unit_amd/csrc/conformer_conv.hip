@@ -64,23 +64,34 @@ __global__ __launch_bounds__(256) void glu_dwconv_kernel(const uint16_t* __restr
 int l2s_f32_glu_dwconv_swish(const void* x, const float* w, const float* bias, void* y, const int32_t* lens, int len_mul, int B, int T,
                              int C, int k, hipStream_t st);
 
-extern "C" int l2s_glu_dwconv_swish(const void* x, const float* w, const float* bias, void* y, const int32_t* lens,
-                                    int len_mul, int B, int T, int C, int k, int dtype, void* stream) {
-  if (!x || !w || !bias || !y) return L2S_EINVAL;
+// Which tile a launch runs on (or the error the launch answers): the one place the dispatch is decided, shared by
+// l2s_glu_dwconv_swish and the host-only query l2s_glu_dwconv_tile.
+static int glu_dwconv_select(int B, int T, int C, int k, int dtype) {
   if (B <= 0 || T <= 0 || C <= 0) return L2S_ESHAPE;
   if (k <= 0 || k > KMAX || !(k & 1)) return L2S_EUNSUPPORTED;
   if (C % CT) return L2S_EALIGN;
-  if (dtype == L2S_F32) return l2s_f32_glu_dwconv_swish(x, w, bias, y, lens, len_mul, B, T, C, k, (hipStream_t)stream);
+  if (dtype == L2S_F32) return L2S_SEQ_VARIANT_F32;
+  if (dtype != L2S_F16 && dtype != L2S_BF16) return L2S_EINVAL;
   // rows computed = tiles * TT: take the tile length that wastes fewer of them (ties: the longer tile, less halo)
   const int r128 = ((T + 127) / 128) * 128, r100 = ((T + 99) / 100) * 100;
   const bool use100 = r100 + ((T + 99) / 100) * 10 < r128 + ((T + 127) / 128) * 10;
-  const int TTr = use100 ? 100 : 128;
+  return use100 ? 100 : 128;
+}
+
+extern "C" int l2s_glu_dwconv_tile(int B, int T, int C, int k, int dtype) { return glu_dwconv_select(B, T, C, k, dtype); }
+
+extern "C" int l2s_glu_dwconv_swish(const void* x, const float* w, const float* bias, void* y, const int32_t* lens,
+                                    int len_mul, int B, int T, int C, int k, int dtype, void* stream) {
+  if (!x || !w || !bias || !y) return L2S_EINVAL;
+  const int TTr = glu_dwconv_select(B, T, C, k, dtype);
+  if (TTr < 0) return TTr;
+  if (TTr == L2S_SEQ_VARIANT_F32) return l2s_f32_glu_dwconv_swish(x, w, bias, y, lens, len_mul, B, T, C, k, (hipStream_t)stream);
+  const bool use100 = TTr == 100;
   dim3 grid((T + TTr - 1) / TTr, C / CT, B), blk(256);
   hipStream_t st = (hipStream_t)stream;
 #define GLU_LAUNCH(ET_, TT_) hipLaunchKernelGGL((glu_dwconv_kernel<ET_, TT_>), grid, blk, 0, st, (const uint16_t*)x, w, bias, (uint16_t*)y, lens, len_mul, T, C, k)
   if (dtype == L2S_F16) { if (use100) GLU_LAUNCH(ElemF16, 100); else GLU_LAUNCH(ElemF16, 128); }
-  else if (dtype == L2S_BF16) { if (use100) GLU_LAUNCH(ElemBF16, 100); else GLU_LAUNCH(ElemBF16, 128); }
-  else return L2S_EINVAL;
+  else { if (use100) GLU_LAUNCH(ElemBF16, 100); else GLU_LAUNCH(ElemBF16, 128); }
 #undef GLU_LAUNCH
   L2S_CHECK_LAUNCH();
   return L2S_OK;

@@ -254,28 +254,40 @@ int launch_splitk_ln(const float* P, int ldp, int S, float* x, int ldx, const fl
   return L2S_OK;
 }
 
+// Which kernel a launch runs on (or the error the launch answers): the one place the dispatch is decided, shared by l2s_layernorm
+// and the host-only query l2s_layernorm_variant.  No pointer is dereferenced.
+int layernorm_select(const void* x, int xf, int ldx, const float* gamma, const float* beta, const void* y, int yf, int ldy,
+                     const void* y2, int ldy2, int M, int C, int zp, const int32_t* lens, int len_mul, int mask_T, int dtype) {
+  if (!x || !gamma || !beta || !y) return L2S_EINVAL;
+  if (M <= 0 || C <= 0 || zp < 0) return L2S_ESHAPE;
+  if (C > MAXV4 * 64 * 4) return L2S_EUNSUPPORTED;
+  if (lens && (len_mul <= 0 || mask_T <= 0)) return L2S_EINVAL;
+  if ((C & 3) || (zp & 3) || (ldx & 3) || (ldy & 3) || (y2 && (ldy2 & 3))) return L2S_EALIGN;
+  if (dtype == L2S_F32) return L2S_SEQ_VARIANT_F32;   // x, y and y2 are all fp32
+  if (dtype != L2S_F16 && dtype != L2S_BF16) return L2S_EINVAL;
+  static const int rows_on = [] { const char* e = getenv("L2S_LN_ROWS"); return e ? atoi(e) : 1; }();   // A/B switch
+  if (rows_on && xf && !y2 && zp == 0 && (C == 1024 || C == 512) && (yf || (((uintptr_t)y & 15) == 0 && (ldy & 7) == 0)))
+    return C + (yf ? 1 : 0);                                   // layernorm_rows_kernel<ET, C / 256, 2048 / C, yf>
+  return L2S_LN_GENERIC + (xf ? 2 : 0) + (yf ? 1 : 0);         // layernorm_kernel<ET, xf, yf>
+}
+
 template <typename ET>
-int launch_ln(const void* x, int xf, int ldx, const float* g, const float* b, float eps, void* y, int yf, int ldy,
+int launch_ln(int var, const void* x, int ldx, const float* g, const float* b, float eps, void* y, int ldy,
               uint16_t* y2, int ldy2, int M, int C, int zp, const int32_t* lens, int len_mul, int mask_T, hipStream_t st) {
   dim3 grid((M + 3) / 4), block(256);
-  static const int rows_on = [] { const char* e = getenv("L2S_LN_ROWS"); return e ? atoi(e) : 1; }();   // A/B switch
-  if (rows_on && xf && !y2 && zp == 0 && (C == 1024 || C == 512) && (yf || (((uintptr_t)y & 15) == 0 && (ldy & 7) == 0))) {
+  if (var >= 512) {
     const float* xf32 = (const float*)x;
-    if (C == 1024) {
-      dim3 g2((M + 7) / 8);
-      if (yf) hipLaunchKernelGGL((layernorm_rows_kernel<ET, 4, 2, true>), g2, block, 0, st, xf32, ldx, g, b, eps, y, ldy, M, lens, len_mul, mask_T);
-      else hipLaunchKernelGGL((layernorm_rows_kernel<ET, 4, 2, false>), g2, block, 0, st, xf32, ldx, g, b, eps, y, ldy, M, lens, len_mul, mask_T);
-    } else {
-      dim3 g4((M + 15) / 16);
-      if (yf) hipLaunchKernelGGL((layernorm_rows_kernel<ET, 2, 4, true>), g4, block, 0, st, xf32, ldx, g, b, eps, y, ldy, M, lens, len_mul, mask_T);
-      else hipLaunchKernelGGL((layernorm_rows_kernel<ET, 2, 4, false>), g4, block, 0, st, xf32, ldx, g, b, eps, y, ldy, M, lens, len_mul, mask_T);
-    }
+    dim3 g2((M + 7) / 8), g4((M + 15) / 16);
+    if (var == 1025) hipLaunchKernelGGL((layernorm_rows_kernel<ET, 4, 2, true>), g2, block, 0, st, xf32, ldx, g, b, eps, y, ldy, M, lens, len_mul, mask_T);
+    else if (var == 1024) hipLaunchKernelGGL((layernorm_rows_kernel<ET, 4, 2, false>), g2, block, 0, st, xf32, ldx, g, b, eps, y, ldy, M, lens, len_mul, mask_T);
+    else if (var == 513) hipLaunchKernelGGL((layernorm_rows_kernel<ET, 2, 4, true>), g4, block, 0, st, xf32, ldx, g, b, eps, y, ldy, M, lens, len_mul, mask_T);
+    else hipLaunchKernelGGL((layernorm_rows_kernel<ET, 2, 4, false>), g4, block, 0, st, xf32, ldx, g, b, eps, y, ldy, M, lens, len_mul, mask_T);
     L2S_CHECK_LAUNCH();
     return L2S_OK;
   }
-  if (xf && yf) hipLaunchKernelGGL((layernorm_kernel<ET, true, true>), grid, block, 0, st, x, ldx, g, b, eps, y, ldy, y2, ldy2, M, C, zp, lens, len_mul, mask_T);
-  else if (xf) hipLaunchKernelGGL((layernorm_kernel<ET, true, false>), grid, block, 0, st, x, ldx, g, b, eps, y, ldy, y2, ldy2, M, C, zp, lens, len_mul, mask_T);
-  else if (yf) hipLaunchKernelGGL((layernorm_kernel<ET, false, true>), grid, block, 0, st, x, ldx, g, b, eps, y, ldy, y2, ldy2, M, C, zp, lens, len_mul, mask_T);
+  if (var == L2S_LN_GENERIC + 3) hipLaunchKernelGGL((layernorm_kernel<ET, true, true>), grid, block, 0, st, x, ldx, g, b, eps, y, ldy, y2, ldy2, M, C, zp, lens, len_mul, mask_T);
+  else if (var == L2S_LN_GENERIC + 2) hipLaunchKernelGGL((layernorm_kernel<ET, true, false>), grid, block, 0, st, x, ldx, g, b, eps, y, ldy, y2, ldy2, M, C, zp, lens, len_mul, mask_T);
+  else if (var == L2S_LN_GENERIC + 1) hipLaunchKernelGGL((layernorm_kernel<ET, false, true>), grid, block, 0, st, x, ldx, g, b, eps, y, ldy, y2, ldy2, M, C, zp, lens, len_mul, mask_T);
   else hipLaunchKernelGGL((layernorm_kernel<ET, false, false>), grid, block, 0, st, x, ldx, g, b, eps, y, ldy, y2, ldy2, M, C, zp, lens, len_mul, mask_T);
   L2S_CHECK_LAUNCH();
   return L2S_OK;
@@ -287,22 +299,23 @@ int launch_ln(const void* x, int xf, int ldx, const float* g, const float* b, fl
 int l2s_f32_layernorm(const void* x, int ldx, const float* gamma, const float* beta, float eps, void* y, int ldy, void* y2, int ldy2,
                       int M, int C, int zp, const int32_t* lens, int len_mul, int mask_T, hipStream_t st);
 
+extern "C" int l2s_layernorm_variant(const void* x, int x_is_f32, int ldx, const float* gamma, const float* beta, const void* y,
+                                     int y_is_f32, int ldy, const void* y2, int ldy2, int M, int C, int zero_prefix,
+                                     const int32_t* lens, int len_mul, int mask_T, int dtype) {
+  return layernorm_select(x, x_is_f32, ldx, gamma, beta, y, y_is_f32, ldy, y2, ldy2, M, C, zero_prefix, lens, len_mul, mask_T, dtype);
+}
+
 extern "C" int l2s_layernorm(const void* x, int x_is_f32, int ldx, const float* gamma, const float* beta, float eps,
                              void* y, int y_is_f32, int ldy, void* y2, int ldy2, int M, int C, int zero_prefix,
                              const int32_t* lens, int len_mul, int mask_T, int dtype, void* stream) {
-  if (!x || !gamma || !beta || !y) return L2S_EINVAL;
-  if (M <= 0 || C <= 0 || zero_prefix < 0) return L2S_ESHAPE;
-  if (C > MAXV4 * 64 * 4) return L2S_EUNSUPPORTED;
-  if (lens && (len_mul <= 0 || mask_T <= 0)) return L2S_EINVAL;
-  if ((C & 3) || (zero_prefix & 3) || (ldx & 3) || (ldy & 3) || (y2 && (ldy2 & 3))) return L2S_EALIGN;
+  const int var = layernorm_select(x, x_is_f32, ldx, gamma, beta, y, y_is_f32, ldy, y2, ldy2, M, C, zero_prefix, lens, len_mul, mask_T, dtype);
+  if (var < 0) return var;
   hipStream_t st = (hipStream_t)stream;
-  if (dtype == L2S_F32)   // x, y and y2 are all fp32
+  if (var == L2S_SEQ_VARIANT_F32)
     return l2s_f32_layernorm(x, ldx, gamma, beta, eps, y, ldy, y2, ldy2, M, C, zero_prefix, lens, len_mul, mask_T, st);
   if (dtype == L2S_F16)
-    return launch_ln<ElemF16>(x, x_is_f32, ldx, gamma, beta, eps, y, y_is_f32, ldy, (uint16_t*)y2, ldy2, M, C, zero_prefix, lens, len_mul, mask_T, st);
-  if (dtype == L2S_BF16)
-    return launch_ln<ElemBF16>(x, x_is_f32, ldx, gamma, beta, eps, y, y_is_f32, ldy, (uint16_t*)y2, ldy2, M, C, zero_prefix, lens, len_mul, mask_T, st);
-  return L2S_EINVAL;
+    return launch_ln<ElemF16>(var, x, ldx, gamma, beta, eps, y, ldy, (uint16_t*)y2, ldy2, M, C, zero_prefix, lens, len_mul, mask_T, st);
+  return launch_ln<ElemBF16>(var, x, ldx, gamma, beta, eps, y, ldy, (uint16_t*)y2, ldy2, M, C, zero_prefix, lens, len_mul, mask_T, st);
 }
 
 extern "C" int l2s_splitk_reduce_layernorm(const float* P, int ldp, int S, float* x, int ldx, const float* gamma, const float* beta,

@@ -80,10 +80,10 @@ def _attn_ref(q, k, v, lens, pos=None, u=None, vb=None):
                                           (1, 300, 2, True), (1, 130, 2, False), (1, 600, 2, True),
                                           (2, 250, 4, False), (2, 64, 2, False), (2, 65, 2, True), (2, 128, 2, True),
                                           (1, 1, 1, False), (1, 513, 1, True),
-                                          # sequence-resident rel-pos kernel (T <= 224): more clips than block slots, ragged
-                                          # lengths, the largest T it takes, tiny T
-                                          (70, 200, 8, True), (3, 224, 8, True), (2, 17, 8, True), (5, 1, 2, True),
-                                          (40, 33, 8, True), (2, 225, 8, True),
+                                          # sequence-resident rel-pos kernel (T <= 208): more clips than block slots, ragged
+                                          # lengths, the largest T it takes (208; 209, 224 and 225 run on the tiled kernel), tiny T
+                                          (70, 200, 8, True), (3, 208, 8, True), (2, 209, 8, True), (3, 224, 8, True),
+                                          (2, 17, 8, True), (5, 1, 2, True), (40, 33, 8, True), (2, 225, 8, True),
                                           # the 24-s clips: conformer rel-pos at T = 1200 (2 399 positions) on the tiled
                                           # kernel's 128-row query blocks, alone and ragged; encoder attention at T = 600, H = 16
                                           (1, 1200, 8, True), (2, 1200, 8, True), (2, 600, 16, False)])
@@ -136,10 +136,11 @@ def _attn_ref_rounded(q, k, v, lens, pos, u, vb, dt):
 
 @pytest.mark.parametrize("dt", [ops.F16, ops.BF16])
 @pytest.mark.parametrize("T,lens", [(150, [150, 97]), (200, [200, 101]), (100, [99, 100]), (257, [257, 3]), (31, [31, 1]),
-                                    (1200, [1200, 50])])
+                                    (1200, [1200, 50]), (128, [128, 101]), (250, [250, 129])])
 def test_glu_dwconv_swish(dt, T, lens):
-    """T = 150, 257, 31 run on the 128-step tile, T = 200 / 100 on the 100-step tile (the launcher takes whichever wastes
-    fewer rows); ragged lengths, a clip shorter than the conv's half-width."""
+    """T = 128 and 250 run on the 128-step tile, every other T here on the 100-step tile (the launcher takes whichever computes
+    fewer rows and halos: the 128-step tile only for T in 101..128, 201..256, 301..384, 501..512); ragged lengths, a clip shorter
+    than the conv's half-width.  Every tile edge, width and kernel size: tests/test_seq_matrix_gpu.py."""
     B, C, k = 2, 128, 31
     g = torch.Generator().manual_seed(3 + T)
     x = _r16(torch.randn(B, T, 2 * C, generator=g), dt)
