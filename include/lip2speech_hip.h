@@ -620,6 +620,55 @@ int l2s_kmeans_pp_pot(const float* x, int ldx, int64_t N, const int32_t* rows, i
 int l2s_kmeans_pp_pick(const float* closest, int m, const double* u, int t, const double* scale, int32_t* idx, double* total,
                        void* stream);
 
+/*
+ * Objective intelligibility of processed speech against its clean original, the numbers the reference publishes for every model
+ * (README.md:103-122: STOI / ESTOI), csrc/stoi.hip; the host class is lip2speech_unit_amd/intelligibility.py.  Neither measure
+ * is in the reference tree; they are the published algorithms of
+ *   STOI:  C. H. Taal, R. C. Hendriks, R. Heusdens, J. Jensen, "An algorithm for intelligibility prediction of time-frequency
+ *          weighted noisy speech", IEEE Trans. Audio, Speech, Language Process. 19(7), 2011;
+ *   ESTOI: J. Jensen, C. H. Taal, "An algorithm for predicting the intelligibility of speech masked by modulated noise maskers",
+ *          IEEE/ACM Trans. Audio, Speech, Language Process. 24(11), 2016,
+ * as restated in DESIGN.md section 17 (its steps 1-6 are cited below).  Four entries, one per observable stage.  Common to them:
+ * clips are 16 kHz; n_samples: int32 [B] clip lengths (clamped to [0, S]) or NULL = S; a clip of n samples has
+ * len = ceil(5 n / 8) samples at 10 kHz and frames(len) = ceil((len - 256) / 128) analysis frames (0 up to 256 samples).
+ * Supported: S <= 419 840 (26 s: 2 048 frames), B <= 65535; more returns L2S_EUNSUPPORTED before anything is launched.  No
+ * entry uses an atomic: a clip's results are the same bytes from run to run and whatever its batch mates are.
+ *
+ * l2s_stoi_resample - step 1 (Taal et al. section II: 10 kHz; the Octave-compatible resampler of the published code), one signal:
+ *   wav: [B, S] with leading dimension ldw, fp32 in (-1, 1) or (wav_is_i16) int16 PCM taken as value / 32768;
+ *   taps: fp32 [5][117], taps[p][q] = 5 w[p + 5 q] of the 581 normalised Kaiser taps w (0 where p + 5 q > 580);
+ *   out: fp32 rows of R >= ceil(5 S / 8) samples, row b at out + b*ldo:  out[m] = sum_q taps[p][q] x[(8 m + 290 - p) / 5 - q],
+ *   p = 3 m mod 5, q ascending as one fp32 fma chain, x = 0 outside the clip; zero for m >= len_b.
+ * l2s_stoi_frames - step 2 (Taal et al. section II: frames 40 dB below the loudest are dropped), on the resampled CLEAN signal:
+ *   x: fp32 rows (ldx >= ceil(5 S / 8)); window: fp32 [256] = hanning(258)[1:-1];
+ *   kept: int32 [B, ldk], ldk >= frames(ceil(5 S / 8)): the indices j (ascending) of the frames with
+ *   norm_j + 2^-52 > (max_j norm_j + 2^-52) / 100, norm_j = |window * x[128 j .. + 256)| with the squares summed in fp64; -1 past
+ *   n_kept[b], the count.
+ * l2s_stoi_bands - steps 2-3 (overlap-add of the kept frames; Taal et al. eq. (1): third-octave band magnitudes):
+ *   x, y: the resampled clean and processed signals (same ldx); kept / n_kept as above (an index outside the clip's frames is
+ *   skipped); basis: fp32 [256][512], 16-byte aligned, row n = sample of a frame with window[n] folded in, column
+ *   c -> pass c / 256, wave (c % 256) / 64, part (c % 64) / 32 (0: cos, 1: -sin), lane c % 32, bin 7 + 128 pass + 32 wave + lane
+ *   of the 512-point DFT (bins past 218 are not used); band_edges: int32 [16], band i sums bins [edges[i], edges[i+1]) within [7, 219);
+ *   bands: fp32 [B, 2, 15, ldf] (0: clean, 1: processed), ldf >= frames - 1: column f < F_b = max(n_kept[b] - 1, 0) holds
+ *   sqrt(sum over the band's bins, ascending, of re^2 + im^2) of frame f of the compacted signal, columns F_b <= f < ldf zeros.
+ *   The compacted signal and the spectrum exist in LDS and registers only.
+ * l2s_stoi_scores - steps 4-6 (Taal et al. eqs. (2)-(6) with N = 30, beta = -15 dB; Jensen & Taal eqs. (4)-(9)):
+ *   seg: doubles [B, 2, lds], lds >= max(ldf - 29, 1): workspace; afterwards seg[b][0][s] = the sum over bands of segment s's
+ *   clipped correlation, seg[b][1][s] = its ESTOI term, for s < n_segments[b] (the rest is unspecified);
+ *   stoi / estoi: fp32 [B] = their means over the clip's segments (STOI also over the 15 bands), n_segments: int32 [B] =
+ *   max(F_b - 29, 0); a clip without a segment gets 1e-5 for both, as the published code returns.  Terms are fp32, the sums
+ *   over bands, frames and segments fp64 in index order.
+ */
+int l2s_stoi_resample(const void* wav, int wav_is_i16, int64_t ldw, const int32_t* n_samples, int B, int S, const float* taps,
+                      float* out, int64_t ldo, int R, void* stream);
+int l2s_stoi_frames(const float* x, int64_t ldx, const int32_t* n_samples, int B, int S, const float* window, int32_t* kept, int ldk,
+                    int32_t* n_kept, void* stream);
+int l2s_stoi_bands(const float* x, const float* y, int64_t ldx, const int32_t* n_samples, int B, int S, const int32_t* kept, int ldk,
+                   const int32_t* n_kept, const float* window, const float* basis, const int32_t* band_edges, float* bands, int ldf,
+                   void* stream);
+int l2s_stoi_scores(const float* bands, int ldf, const int32_t* n_kept, int B, double* seg, int lds, float* stoi, float* estoi,
+                    int32_t* n_segments, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

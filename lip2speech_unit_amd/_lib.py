@@ -125,6 +125,10 @@ SIGNATURES = {
     "l2s_kmeans_pp_workspace": ([_i], ctypes.c_size_t),
     "l2s_kmeans_pp_pot": ([_vp, _i, ctypes.c_int64, _vp, _i, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, ctypes.c_size_t, _vp], _i),
     "l2s_kmeans_pp_pick": ([_vp, _i, _vp, _i, _vp, _vp, _vp, _vp], _i),
+    "l2s_stoi_resample": ([_vp, _i, ctypes.c_int64, _vp, _i, _i, _vp, _vp, ctypes.c_int64, _i, _vp], _i),
+    "l2s_stoi_frames": ([_vp, ctypes.c_int64, _vp, _i, _i, _vp, _vp, _i, _vp, _vp], _i),
+    "l2s_stoi_bands": ([_vp, _vp, ctypes.c_int64, _vp, _i, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp, _i, _vp], _i),
+    "l2s_stoi_scores": ([_vp, _i, _vp, _i, _vp, _i, _vp, _vp, _vp, _vp], _i),
 }
 
 _lib = None

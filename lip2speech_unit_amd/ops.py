@@ -827,6 +827,92 @@ def kmeans_pp_pick(closest, u, idx, *, m, t, scale=None, total=None):
         _ptr(closest), m, _ptr(u) if t else None, t, _ptr(scale), _ptr(idx), _ptr(total), _stream()), nbytes=4.0 * m * (1 + t))
 
 
+STOI_MAX_SAMPLES = 419840   # csrc/stoi.hip: the longest 16 kHz clip (2 048 analysis frames at 10 kHz); longer is L2S_EUNSUPPORTED
+
+
+def stoi_len10k(n):
+    """Samples at 10 kHz of n samples at 16 kHz: ceil(5 n / 8)."""
+    return (5 * n + 7) // 8
+
+
+def stoi_frames_of(n10k):
+    """Analysis frames (256 samples, hop 128, starts i < len - 256) of a 10 kHz signal."""
+    return (n10k - 257) // 128 + 1 if n10k > 256 else 0
+
+
+def _stoi_common(name, n_samples, B, S):
+    if n_samples is not None:
+        _req(n_samples, torch.int32, "n_samples")
+        if n_samples.numel() < B:
+            raise L2SError(f"{name}: n_samples shorter than B")
+
+
+def stoi_resample(wav, taps, out, *, B, S, R, n_samples=None, ldw=None, ldo=None):
+    """STOI step 1 (csrc/stoi.hip): wav fp32 or int16 [B, S] at 16 kHz -> out fp32 rows of R >= ceil(5 S / 8) samples at 10 kHz
+    (row stride ldo), the 581-tap Kaiser polyphase FIR with taps fp32 [5, 117]; zeros past each clip's own ceil(5 n_b / 8)."""
+    if wav.dtype not in (torch.float32, torch.int16):
+        raise L2SError(f"wav: expected float32 or int16, got {wav.dtype}")
+    _req(wav, None, "wav"), _req(taps, torch.float32, "taps"), _req(out, torch.float32, "out")
+    _stoi_common("stoi_resample", n_samples, B, S)
+    ldw = ldw if ldw is not None else S
+    ldo = ldo if ldo is not None else R
+    if (B - 1) * ldw + S > _extent(wav) or (B - 1) * ldo + R > _extent(out) or taps.numel() < 5 * 117 or not taps.is_contiguous():
+        raise L2SError("stoi_resample: wav smaller than [B, S] of ldw, out smaller than [B, R] of ldo, or taps not [5, 117]")
+    _run("l2s_stoi_resample", lambda: _lib.load().l2s_stoi_resample(
+        _ptr(wav), int(wav.dtype == torch.int16), ldw, _ptr(n_samples), B, S, _ptr(taps), _ptr(out), ldo, R, _stream()),
+        flops=2.0 * 117 * B * R, nbytes=float(B) * S * wav.element_size() + 4.0 * B * R)
+
+
+def stoi_frames(x, window, kept, n_kept, *, B, S, n_samples=None, ldx=None, ldk=None):
+    """STOI step 2 (csrc/stoi.hip): the frames of the resampled clean signal x (fp32 rows, stride ldx) within 40 dB of the loudest:
+    kept int32 [B, ldk] ascending indices, -1 past n_kept int32 [B]."""
+    _req(x, torch.float32, "x"), _req(window, torch.float32, "window"), _req(kept, torch.int32, "kept"), _req(n_kept, torch.int32, "n_kept")
+    _stoi_common("stoi_frames", n_samples, B, S)
+    ldx = ldx if ldx is not None else x.stride(0)
+    ldk = ldk if ldk is not None else kept.stride(0)
+    if (B - 1) * ldx + stoi_len10k(S) > _extent(x) or (B - 1) * ldk + ldk > _extent(kept) or n_kept.numel() < B or window.numel() < 256:
+        raise L2SError("stoi_frames: x smaller than [B, ceil(5 S / 8)] of ldx, kept smaller than [B, ldk], n_kept shorter than B or window < 256")
+    _run("l2s_stoi_frames", lambda: _lib.load().l2s_stoi_frames(
+        _ptr(x), ldx, _ptr(n_samples), B, S, _ptr(window), _ptr(kept), ldk, _ptr(n_kept), _stream()), nbytes=4.0 * B * stoi_len10k(S))
+
+
+def stoi_bands(x, y, kept, n_kept, window, basis, band_edges, bands, *, B, S, ldf, n_samples=None, ldx=None, ldk=None):
+    """STOI steps 2-3 (csrc/stoi.hip): third-octave band magnitudes bands fp32 [B, 2, 15, ldf] of the kept frames of the resampled
+    clean (x) and processed (y) signals, overlap-added in LDS; basis fp32 [256, 512], band_edges int32 [16]."""
+    for t, n in ((x, "x"), (y, "y"), (window, "window"), (basis, "basis"), (bands, "bands")):
+        _req(t, torch.float32, n)
+    _req(kept, torch.int32, "kept"), _req(n_kept, torch.int32, "n_kept"), _req(band_edges, torch.int32, "band_edges")
+    _stoi_common("stoi_bands", n_samples, B, S)
+    ldx = ldx if ldx is not None else x.stride(0)
+    ldk = ldk if ldk is not None else kept.stride(0)
+    if x.stride(0) != y.stride(0) and B > 1:
+        raise L2SError("stoi_bands: x and y need the same row stride")
+    if (B - 1) * ldx + stoi_len10k(S) > min(_extent(x), _extent(y)) or (B - 1) * ldk + ldk > _extent(kept) or n_kept.numel() < B:
+        raise L2SError("stoi_bands: x / y smaller than [B, ceil(5 S / 8)] of ldx, kept smaller than [B, ldk] or n_kept shorter than B")
+    if window.numel() < 256 or basis.numel() < 256 * 512 or not basis.is_contiguous() or band_edges.numel() < 16:
+        raise L2SError("stoi_bands: tables smaller than [256], [256, 512], [16]")
+    if not bands.is_contiguous() or bands.numel() < B * 2 * 15 * ldf:
+        raise L2SError("stoi_bands: bands must be dense [B, 2, 15, ldf]")
+    _run("l2s_stoi_bands", lambda: _lib.load().l2s_stoi_bands(
+        _ptr(x), _ptr(y), ldx, _ptr(n_samples), B, S, _ptr(kept), ldk, _ptr(n_kept), _ptr(window), _ptr(basis), _ptr(band_edges),
+        _ptr(bands), ldf, _stream()), flops=2.0 * 2 * B * ldf * 256 * 512, nbytes=8.0 * B * stoi_len10k(S) + 4.0 * 256 * 512)
+
+
+def stoi_scores(bands, n_kept, seg, stoi, estoi, n_segments, *, B, ldf, lds=None):
+    """STOI steps 4-6 (csrc/stoi.hip): per-clip stoi / estoi fp32 [B] and n_segments int32 [B] from bands fp32 [B, 2, 15, ldf];
+    seg float64 [B, 2, lds] is the workspace that ends holding every segment's two terms."""
+    _req(bands, torch.float32, "bands"), _req(n_kept, torch.int32, "n_kept"), _req(seg, torch.float64, "seg")
+    _req(stoi, torch.float32, "stoi"), _req(estoi, torch.float32, "estoi"), _req(n_segments, torch.int32, "n_segments")
+    lds = lds if lds is not None else seg.shape[-1]
+    if not bands.is_contiguous() or bands.numel() < B * 2 * 15 * ldf or not seg.is_contiguous() or seg.numel() < B * 2 * lds:
+        raise L2SError("stoi_scores: bands must be dense [B, 2, 15, ldf] and seg dense [B, 2, lds]")
+    if min(n_kept.numel(), stoi.numel(), estoi.numel(), n_segments.numel()) < B:
+        raise L2SError("stoi_scores: per-clip tensors shorter than B")
+    _run("l2s_stoi_scores", lambda: _lib.load().l2s_stoi_scores(
+        _ptr(bands), ldf, _ptr(n_kept), B, _ptr(seg), lds, _ptr(stoi), _ptr(estoi), _ptr(n_segments), _stream()),
+        nbytes=4.0 * B * 2 * 15 * ldf)
+
+
 # ---- torch.library registration ("PyTorch-ROCm custom ops", SURVEY 8b last row) --------------------------------------------------
 # Every launcher above is ALSO a dispatcher-visible operator `torch.ops.lip2speech.<name>` (schema below, CUDA = HIP kernel only: a
 # CPU tensor finds no kernel and raises; a fake / meta implementation gives shapes to torch.compile and fake-tensor tracing), and
@@ -932,6 +1018,14 @@ _SCHEMAS = {
                      "Tensor? select=None, Tensor(b!)? pot=None, Tensor(c!)? closest_out=None, Tensor(d!)? chosen=None, "
                      "int? ldx=None) -> ()",
     "kmeans_pp_pick": "(Tensor closest, Tensor u, Tensor(a!) idx, *, int m, int t, Tensor? scale=None, Tensor(b!)? total=None) -> ()",
+    "stoi_resample": "(Tensor wav, Tensor taps, Tensor(a!) out, *, int B, int S, int R, Tensor? n_samples=None, int? ldw=None, "
+                     "int? ldo=None) -> ()",
+    "stoi_frames": "(Tensor x, Tensor window, Tensor(a!) kept, Tensor(b!) n_kept, *, int B, int S, Tensor? n_samples=None, int? ldx=None, "
+                   "int? ldk=None) -> ()",
+    "stoi_bands": "(Tensor x, Tensor y, Tensor kept, Tensor n_kept, Tensor window, Tensor basis, Tensor band_edges, Tensor(a!) bands, *, "
+                  "int B, int S, int ldf, Tensor? n_samples=None, int? ldx=None, int? ldk=None) -> ()",
+    "stoi_scores": "(Tensor bands, Tensor n_kept, Tensor(a!) seg, Tensor(b!) stoi, Tensor(c!) estoi, Tensor(d!) n_segments, *, int B, "
+                   "int ldf, int? lds=None) -> ()",
 }
 # C-ABI entry each operator launches (tests/test_torchlib_cpu.py: every device entry of include/lip2speech_hip.h has a twin)
 ENTRY_OF = {n: "l2s_" + n for n in _SCHEMAS}

@@ -3,11 +3,13 @@
 
   python -m lip2speech_unit_amd.vocoder_inference <config.json> <label/test.tsv> <dict.unt.txt> \
       --output_dir D --checkpoint_file C -n -1 [--pad N] [--synthetic_weights] [--mel_from_audio]
-      [--units_from_audio --hubert <ckpt> --kmeans <km.bin|centers.npy> [--units_layer 6] [--units_dtype f32|f16|bf16]]
+      [--units_from_audio --hubert <ckpt> --kmeans <km.bin|centers.npy> [--units_layer 6] [--units_dtype f32|f16|bf16]] [--stoi]
 --mel_from_audio: the mel conditioning is analysed from audio/*.wav on the device (audio.TacotronSTFT); mel/ is not read.
 --units_from_audio: the units are computed from audio/*.wav on the device (speech_units.SpeechUnitExtractor); the .unt file is
 not read.  With both flags stage 2 runs from a folder of wavs and speaker embeddings alone.
 Writes D/pred_wav/<spk>/<utt>.wav (int16, 16 kHz) like :157-165.
+--stoi (off by default): the clips just written are scored against the manifest's audio on the device (evaluate.report: STOI and
+ESTOI, the summary line and D/eval-stoi.json).
 """
 import argparse
 import json
@@ -35,7 +37,7 @@ def manifest_from_audio(manifest_path, extractor, batch=16):
     return audio_files, mels, [" ".join(str(int(v)) for v in ids) for ids in units]
 
 
-def main(argv=None):
+def build_parser():
     p = argparse.ArgumentParser()
     p.add_argument("config_file")
     p.add_argument("input_code_file")
@@ -54,6 +56,12 @@ def main(argv=None):
     p.add_argument("--kmeans", default=None)
     p.add_argument("--units_layer", type=int, default=6)
     p.add_argument("--units_dtype", default="f32", choices=["f32", "f16", "bf16"])
+    p.add_argument("--stoi", action="store_true", default=argparse.SUPPRESS)   # absent: the namespace is what it was without the flag
+    return p
+
+
+def main(argv=None):
+    p = build_parser()
     a = p.parse_args(argv)
     if a.units_from_audio and not (a.hubert and a.kmeans):
         p.error("--units_from_audio needs --hubert and --kmeans")
@@ -86,6 +94,7 @@ def main(argv=None):
     os.makedirs(a.output_dir, exist_ok=True)
     n = len(ds) if a.n == -1 else min(a.n, len(ds))
     audio_s, wall = 0.0, 0.0
+    written = []
     for i in range(n):
         feats, _, filename, _ = ds[i]
         code = {k: torch.from_numpy(v).cuda().unsqueeze(0) for k, v in feats.items()}        # :155
@@ -98,7 +107,11 @@ def main(argv=None):
         out = os.path.join(a.output_dir, os.path.join("pred_wav", *(filename.split("/")[-2:]))[:-4] + ".wav")
         os.makedirs(os.path.dirname(out), exist_ok=True)
         write(out, h.sampling_rate, audio.astype(np.int16))
+        written.append(("/".join(filename.split("/")[-2:])[:-4], filename, out))
     print(f"synthesised {n} clips, {audio_s:.1f} s of audio in {wall:.2f} s (RTF {audio_s / max(wall, 1e-9):.1f}x)")
+    if getattr(a, "stoi", False):
+        from . import evaluate
+        evaluate.report(written, a.output_dir)
 
 
 if __name__ == "__main__":
