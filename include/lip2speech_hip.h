@@ -669,6 +669,56 @@ int l2s_stoi_bands(const float* x, const float* y, int64_t ldx, const int32_t* n
 int l2s_stoi_scores(const float* bands, int ldf, const int32_t* n_kept, int B, double* seg, int lds, float* stoi, float* estoi,
                     int32_t* n_segments, void* stream);
 
+/*
+ * Speaker embeddings from audio: what helpers.py:185-198 (_get_speaker_embedding -> sv2s.utils.get_speaker_embedding, the GE2E
+ * speaker encoder of Real-Time-Voice-Cloning, none of it in the reference tree) computes for create_dataset.py:94,133 and
+ * server.py:115,207 - a float32 (256,) vector per clip.  The algorithm is restated in DESIGN.md section 18; the host class is
+ * lip2speech_unit_amd/speaker_encoder.py.  Four entries; the input projections of the LSTM run on l2s_tapgemm (L2S_F32).
+ * Everything is fp32 in memory, no entry uses an atomic, and every sum runs in a fixed order: a clip's (a sequence's) result is
+ * the same bytes from run to run and whatever its batch (tile) mates are.
+ *
+ * l2s_wav_gain - the increase-only volume normalisation, csrc/spkemb.hip:
+ *   wav: [B, S] with leading dimension ldw, fp32 in (-1, 1) or (wav_is_i16) int16 PCM taken as value / 32768;
+ *   n_samples: int32 [B] clip lengths (clamped to [0, S]) or NULL = S;
+ *   gain: fp32 [B] = 10^(change / 20) if change = target_dbfs - 10 log10(mean(wav^2)) > 0, else 1; the squares are summed in
+ *   fp64.  A clip without samples or of zeros only has no level and gets 1.
+ * l2s_stft_mel_power - 40-band power mel, librosa 0.8's melspectrogram(sr 16000, n_fft 400, hop 160, n_mels 40) with center = True,
+ *   csrc/spkemb.hip: the sibling of l2s_stft_mel for a frame length that is no multiple of the hop, without sqrt and log.
+ *   frame t = samples [160 t - pad, 160 t - pad + 400) reflected once at either end against n_samples[b], re/im a k-ordered fp32
+ *   fma chain, power = re^2 + im^2 (not contracted), band = sum over fb_range[j] in ascending bin order of fb * power.
+ *   n_samples: int32 [B] ANALYSIS lengths (NULL = S): they set the frame count (n + 2 pad - 400) / 160 + 1 (0 unless n > pad
+ *   and a frame fits) and the reflection, and may exceed S; n_valid: int32 [B] real samples (NULL = n_samples; clamped to
+ *   min(n_samples, S)): positions from n_valid on are zeros and are never read - the zero padding of a clip shorter than its last
+ *   partial window; scale: fp32 [B] or NULL, multiplied into every sample (after the int16 conversion) - l2s_wav_gain's output.
+ *   basis: fp32 [400, 448]: row = sample of the frame, column c -> tile q = c / 32, lane l = c % 32, bin 32 (q / 2) + l; even
+ *   tiles hold w cos, odd tiles -w sin (w: periodic Hann), zero columns for bins past 200; fb: fp32 [40, 201];
+ *   fb_range: int32 [40, 2] = [first, past-last) non-zero bin of each band; mel: fp32 rows (b, t) at mel + (b*T_rows + t)*ldm;
+ *   rows past the clip's frame count are zeros.  Supported: (n_fft, hop, n_mels) = (400, 160, 40), 0 <= pad <= 200, B <= 65535,
+ *   S < 2^30; anything else returns L2S_EUNSUPPORTED.
+ * l2s_lstm_layer - one LSTM layer's recurrence for S sequences of T steps from zero state, csrc/lstm.hip:
+ *   xproj: fp32 [n_rows, ldx >= 1024], the input projection x W_ih^T + b_ih + b_hh with GATE-INTERLEAVED columns: column 4 u + g
+ *   holds gate g (torch order i, f, g, o) of hidden unit u; row_off: int32 [S]: sequence s reads row row_off[s] + t at step t
+ *   (offsets may overlap and come in any order - overlapping windows are gathered without a copy; a row outside [0, n_rows) is
+ *   read as the nearest valid row); w_hh_p: fp32 [256 k][256 u][4 g] = weight_hh[256 g + u][k]; h_seq: NULL or fp32 [S, T, 256];
+ *   h_last: NULL or fp32 [S, 256] = h at step T - 1 (at least one of the two).  One workgroup per 16 sequences, no
+ *   synchronisation between workgroups; products on v_mfma_f32_16x16x4_f32 in a fixed k order, expf / tanhf and IEEE division in
+ *   fp32.  A sequence's result does not depend on S or on the other sequences.  Supported: hidden = 256, any T >= 1, S >= 1,
+ *   n_rows >= T; xproj and w_hh_p 16-byte aligned, ldx a multiple of 4.  Other hidden sizes return L2S_EUNSUPPORTED.
+ * l2s_spk_embed_head - per clip b, over the windows h_last[first[b] .. first[b] + count[b]) (clamped to n_rows rows):
+ *   e = relu(W h + bias), e / (|e| + 1e-5), the mean over the windows in index order, divided by its own L2 norm; norms and the
+ *   mean are carried in fp64.  w_t: fp32 [256 k][256 u] = linear.weight[u][k] (transposed); out: fp32 [B, 256].  A clip whose
+ *   mean is exactly zero (every ReLU output zero, or count = 0) gets zeros, where 0 / 0 would be NaN.  hidden must be 256.
+ */
+int l2s_wav_gain(const void* wav, int wav_is_i16, int64_t ldw, const int32_t* n_samples, int B, int S, float target_dbfs, float* gain,
+                 void* stream);
+int l2s_stft_mel_power(const void* wav, int wav_is_i16, int64_t ldw, const int32_t* n_samples, const int32_t* n_valid,
+                       const float* scale, int B, int S, const float* basis, const float* fb, const int32_t* fb_range, float* mel,
+                       int ldm, int T_rows, int n_fft, int hop, int n_mels, int pad, void* stream);
+int l2s_lstm_layer(const float* xproj, int ldx, int64_t n_rows, const int32_t* row_off, const float* w_hh_p, int S, int T, int hidden,
+                   float* h_seq, float* h_last, void* stream);
+int l2s_spk_embed_head(const float* h_last, int n_rows, const int32_t* first, const int32_t* count, const float* w_t,
+                       const float* bias, int B, int hidden, float* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

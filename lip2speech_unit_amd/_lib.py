@@ -129,6 +129,10 @@ SIGNATURES = {
     "l2s_stoi_frames": ([_vp, ctypes.c_int64, _vp, _i, _i, _vp, _vp, _i, _vp, _vp], _i),
     "l2s_stoi_bands": ([_vp, _vp, ctypes.c_int64, _vp, _i, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp, _i, _vp], _i),
     "l2s_stoi_scores": ([_vp, _i, _vp, _i, _vp, _i, _vp, _vp, _vp, _vp], _i),
+    "l2s_wav_gain": ([_vp, _i, ctypes.c_int64, _vp, _i, _i, _f, _vp, _vp], _i),
+    "l2s_stft_mel_power": ([_vp, _i, ctypes.c_int64, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp], _i),
+    "l2s_lstm_layer": ([_vp, _i, ctypes.c_int64, _vp, _vp, _i, _i, _i, _vp, _vp, _vp], _i),
+    "l2s_spk_embed_head": ([_vp, _i, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp], _i),
 }
 
 _lib = None

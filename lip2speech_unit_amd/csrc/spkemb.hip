@@ -1,0 +1,247 @@
+// The speaker encoder's ends (lip2speech_unit_amd/speaker_encoder.py; the recurrence between them is lstm.hip):
+//
+//   l2s_wav_gain        per-clip volume factor: the increase-only normalisation to -30 dBFS, mean square carried in fp64
+//   l2s_stft_mel_power  40-band POWER mel of 400-sample frames every 160 samples - melspec.hip's sibling for a frame length
+//                       that is no multiple of the hop and a linear-power epilogue (no sqrt, no log)
+//   l2s_spk_embed_head  Linear + ReLU + L2 norm per partial window, mean over a clip's windows, final L2 norm
+//
+// None of them uses an atomic; every sum runs in a fixed order, so a clip's bytes do not depend on its batch mates.
+//
+// Power mel.  A block (4 waves) owns 32 consecutive frames of one clip and stages their sample span (31 * 160 + 400 samples) in LDS
+// as hop-sized rows of stride 161 floats - melspec.hip's layout: the 32 frames of an A fragment sit 161 floats = 33 banks apart.
+// Reflection (against the clip's own analysis length), the zero tail past the clip's real samples, the int16 conversion and the
+// volume factor are applied while staging.  The windowed DFT is a [400, 448] fp32 table, K = 400 rows and 14 column tiles of 32:
+// tile 2 p holds w cos, tile 2 p + 1 holds -w sin of bins 32 p .. 32 p + 31; the columns of bins 201 .. 223 are zero, and adding
+// x * 0 is exact.  Wave w owns the tile pairs w and w + 4 (re and im of a bin in the same lane and register), each a k-ordered fp32
+// fma chain on v_mfma_f32_32x32x2_f32, the table read straight from L2 (it is 700 KB and shared by every block).  Powers
+// re^2 + im^2 (products and sum rounded separately, not contracted) go to LDS, and every thread folds them into 5 band sums of one
+// frame, bins ascending over fb_range.
+#include "l2s_common.h"
+#include <math.h>
+
+namespace {
+
+typedef __attribute__((ext_vector_type(16))) float f32x16_t;
+
+// ---- fixed-order block sum of one double per thread (256 threads); the result is returned to every thread -----------------------
+__device__ __forceinline__ double block_sum_f64(double v, double* sD, int tid) {
+  __syncthreads();                                       // sD may still be read from a previous call
+  sD[tid] = v;
+  __syncthreads();
+#pragma unroll
+  for (int s = 128; s > 0; s >>= 1) {
+    if (tid < s) sD[tid] += sD[tid + s];
+    __syncthreads();
+  }
+  return sD[0];
+}
+
+template <bool I16>
+__global__ __launch_bounds__(256) void wav_gain_kernel(const void* __restrict__ wav_, const int64_t ldw, const int32_t* __restrict__ n_samples,
+                                                       const int S, const double target_dbfs, float* __restrict__ gain) {
+  __shared__ double sD[256];
+  const int tid = threadIdx.x, b = blockIdx.x;
+  int n = n_samples ? n_samples[b] : S;
+  n = max(0, min(n, S));
+  double acc = 0.0;
+  for (int p = tid; p < n; p += 256) {
+    float v;
+    if (I16) v = (float)((const int16_t*)wav_)[(int64_t)b * ldw + p] * (1.0f / 32768.0f);
+    else v = ((const float*)wav_)[(int64_t)b * ldw + p];
+    acc += (double)v * (double)v;
+  }
+  const double ss = block_sum_f64(acc, sD, tid);
+  if (tid == 0) {
+    float g = 1.0f;                                      // an empty or all-zero clip has no level: it is left as it is
+    if (n > 0 && ss > 0.0) {
+      const double change = target_dbfs - 10.0 * log10(ss / (double)n);
+      if (change > 0.0) g = (float)pow(10.0, change / 20.0);
+    }
+    gain[b] = g;
+  }
+}
+
+// ---- power mel ---------------------------------------------------------------------------------------------------------------------
+constexpr int NFFT = 400, HOP = 160, FT = 32, NMEL = 40, NBIN = NFFT / 2 + 1;
+constexpr int NPAIR = 7, NCOL = 64 * NPAIR;              // 7 tile pairs = bins 0 .. 223
+constexpr int SPAN = (FT - 1) * HOP + NFFT, SLD = HOP + 1, SROWS = (SPAN + HOP - 1) / HOP;
+constexpr int LDG = 32 * NPAIR + 1;                      // power tile [FT][225]
+constexpr int KC = 16;                                   // k per chunk: 8 MFMA steps whose table loads are issued together
+static_assert(NFFT % KC == 0 && (SROWS * SLD + FT * LDG) * 4 <= 64 * 1024, "tile shape / static LDS");
+
+template <bool I16>
+__global__ __launch_bounds__(256) void mel_power_kernel(const void* __restrict__ wav_, const int64_t ldw, const int32_t* __restrict__ n_samples,
+                                                        const int32_t* __restrict__ n_valid, const float* __restrict__ scale, const int S,
+                                                        const float* __restrict__ basis, const float* __restrict__ fb,
+                                                        const int32_t* __restrict__ fb_range, float* __restrict__ mel, const int ldm,
+                                                        const int T_rows, const int pad) {
+  __shared__ float sX[SROWS * SLD];
+  __shared__ float sG[FT * LDG];
+  const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int b = blockIdx.y, f0 = blockIdx.x * FT;
+  const int n = n_samples ? n_samples[b] : S;            // the analysis length: frames and reflection (may exceed the buffer)
+  int nv = n_valid ? n_valid[b] : n;                     // the real samples: positions from here on are zeros and are not read
+  nv = max(0, min(min(nv, n), S));
+  const int Tb = (n > pad && n + 2 * pad >= NFFT) ? (n + 2 * pad - NFFT) / HOP + 1 : 0;
+  const int rows = min(FT, T_rows - f0);
+  float* __restrict__ out = mel + ((int64_t)b * T_rows + f0) * ldm;
+  if (f0 >= Tb) {                                        // block-uniform: a tile wholly past the clip's end
+    for (int e = tid; e < rows * NMEL; e += 256) {
+      const int r = e / NMEL;
+      out[(int64_t)r * ldm + (e - r * NMEL)] = 0.f;
+    }
+    return;
+  }
+  {
+    const float g = scale ? scale[b] : 1.0f;
+    const int p0 = f0 * HOP - pad;
+    for (int s = tid; s < SROWS * HOP; s += 256) {
+      int p = p0 + s;
+      p = p < 0 ? -p : p;
+      p = p >= n ? 2 * (n - 1) - p : p;
+      float v = 0.f;
+      if (s < SPAN && (unsigned)p < (unsigned)nv) {
+        if (I16) v = (float)((const int16_t*)wav_)[(int64_t)b * ldw + p] * (1.0f / 32768.0f);
+        else v = ((const float*)wav_)[(int64_t)b * ldw + p];
+        if (scale) v = __fmul_rn(v, g);
+      }
+      const int r = s / HOP;
+      sX[r * SLD + (s - r * HOP)] = v;
+    }
+  }
+  __syncthreads();
+
+  const int lr = lane & 31, lh = lane >> 5;
+  const bool two = wave + 4 < NPAIR;                     // wave-uniform: waves 0 .. 2 own a second tile pair
+  const float* b0 = basis + 64 * wave + lr;
+  const float* b1 = basis + 64 * (two ? wave + 4 : wave) + lr;
+  f32x16_t acc[4];
+#pragma unroll
+  for (int q = 0; q < 4; ++q)
+#pragma unroll
+    for (int e = 0; e < 16; ++e) acc[q][e] = 0.f;
+  for (int k0 = 0; k0 < NFFT; k0 += KC) {
+    float w[KC / 2][4];
+#pragma unroll
+    for (int s = 0; s < KC / 2; ++s) {
+      const int k = k0 + 2 * s + lh;
+      w[s][0] = b0[k * NCOL];
+      w[s][1] = b0[k * NCOL + 32];
+      if (two) {
+        w[s][2] = b1[k * NCOL];
+        w[s][3] = b1[k * NCOL + 32];
+      }
+    }
+#pragma unroll
+    for (int s = 0; s < KC / 2; ++s) {
+      const int k = k0 + 2 * s + lh;
+      const int q = k / HOP;
+      const float a = sX[(lr + q) * SLD + (k - q * HOP)];
+      acc[0] = __builtin_amdgcn_mfma_f32_32x32x2f32(a, w[s][0], acc[0], 0, 0, 0);
+      acc[1] = __builtin_amdgcn_mfma_f32_32x32x2f32(a, w[s][1], acc[1], 0, 0, 0);
+      if (two) {
+        acc[2] = __builtin_amdgcn_mfma_f32_32x32x2f32(a, w[s][2], acc[2], 0, 0, 0);
+        acc[3] = __builtin_amdgcn_mfma_f32_32x32x2f32(a, w[s][3], acc[3], 0, 0, 0);
+      }
+    }
+  }
+#pragma unroll
+  for (int e = 0; e < 16; ++e) {
+    const int fr = 8 * (e >> 2) + 4 * lh + (e & 3);
+    sG[fr * LDG + 32 * wave + lr] = __fadd_rn(__fmul_rn(acc[0][e], acc[0][e]), __fmul_rn(acc[1][e], acc[1][e]));
+    if (two) sG[fr * LDG + 32 * (wave + 4) + lr] = __fadd_rn(__fmul_rn(acc[2][e], acc[2][e]), __fmul_rn(acc[3][e], acc[3][e]));
+  }
+  __syncthreads();
+
+  const int mf = tid & (FT - 1), mg = tid / FT;          // frame, band group (5 bands each)
+  if (mf < rows) {
+#pragma unroll
+    for (int j = 0; j < NMEL / 8; ++j) {
+      const int band = mg * (NMEL / 8) + j;
+      const int lo = max(fb_range[2 * band], 0), hi = min(fb_range[2 * band + 1], NBIN);
+      const float* w = fb + band * NBIN;
+      float m = 0.f;
+      for (int k = lo; k < hi; ++k) m = fmaf(w[k], sG[mf * LDG + k], m);
+      out[(int64_t)mf * ldm + band] = f0 + mf < Tb ? m : 0.f;
+    }
+  }
+}
+
+// ---- head --------------------------------------------------------------------------------------------------------------------------
+constexpr int HID = 256;
+
+__global__ __launch_bounds__(HID) void spk_head_kernel(const float* __restrict__ h_last, const int n_rows, const int32_t* __restrict__ first,
+                                                       const int32_t* __restrict__ count, const float* __restrict__ w_t,
+                                                       const float* __restrict__ bias, float* __restrict__ out) {
+  __shared__ double sD[HID];
+  __shared__ float sHv[HID];
+  const int u = threadIdx.x, b = blockIdx.x;
+  const int f = min(max(first[b], 0), n_rows);
+  const int n = max(0, min(count[b], n_rows - f));       // windows outside h_last do not exist
+  const float bu = bias[u];
+  double mean = 0.0;
+  for (int p = 0; p < n; ++p) {
+    __syncthreads();
+    sHv[u] = h_last[(int64_t)(f + p) * HID + u];
+    __syncthreads();
+    float a = bu;
+    for (int k = 0; k < HID; ++k) a = fmaf(w_t[k * HID + u], sHv[k], a);
+    const float e = fmaxf(a, 0.f);
+    const double ss = block_sum_f64((double)e * (double)e, sD, u);
+    mean += (double)e / (sqrt(ss) + 1e-5);               // windows in index order
+  }
+  if (n > 0) mean /= (double)n;
+  const double vv = block_sum_f64(mean * mean, sD, u);
+  // every window's ReLU output zero (or no window): the mean has no direction - zeros, not 0 / 0
+  out[(int64_t)b * HID + u] = vv > 0.0 ? (float)(mean / sqrt(vv)) : 0.f;
+}
+
+}  // namespace
+
+extern "C" int l2s_wav_gain(const void* wav, int wav_is_i16, int64_t ldw, const int32_t* n_samples, int B, int S, float target_dbfs,
+                            float* gain, void* stream) {
+  if (!wav || !gain) return L2S_EINVAL;
+  if (B <= 0 || S <= 0 || ldw < S) return L2S_ESHAPE;
+  if (S >= (1 << 30)) return L2S_EUNSUPPORTED;
+  if (((uintptr_t)wav & (wav_is_i16 ? 1 : 3)) || ((uintptr_t)gain & 3) || ((uintptr_t)n_samples & 3)) return L2S_EALIGN;
+  dim3 grid((unsigned)B), blk(256);
+  if (wav_is_i16) hipLaunchKernelGGL(wav_gain_kernel<true>, grid, blk, 0, (hipStream_t)stream, wav, ldw, n_samples, S, (double)target_dbfs, gain);
+  else hipLaunchKernelGGL(wav_gain_kernel<false>, grid, blk, 0, (hipStream_t)stream, wav, ldw, n_samples, S, (double)target_dbfs, gain);
+  L2S_CHECK_LAUNCH();
+  return L2S_OK;
+}
+
+extern "C" int l2s_stft_mel_power(const void* wav, int wav_is_i16, int64_t ldw, const int32_t* n_samples, const int32_t* n_valid,
+                                  const float* scale, int B, int S, const float* basis, const float* fb, const int32_t* fb_range,
+                                  float* mel, int ldm, int T_rows, int n_fft, int hop, int n_mels, int pad, void* stream) {
+  if (!wav || !basis || !fb || !fb_range || !mel) return L2S_EINVAL;
+  if (B <= 0 || S <= 0 || T_rows <= 0 || n_fft <= 0 || hop <= 0 || n_mels <= 0) return L2S_ESHAPE;
+  if (ldw < S || ldm < n_mels) return L2S_ESHAPE;
+  if (n_fft != NFFT || hop != HOP || n_mels != NMEL) return L2S_EUNSUPPORTED;
+  if (pad < 0 || pad > n_fft / 2) return L2S_EUNSUPPORTED;
+  if (B > 65535 || S >= (1 << 30) || T_rows > (1 << 22)) return L2S_EUNSUPPORTED;   // grid.y; 32-bit sample positions
+  if (((uintptr_t)wav & (wav_is_i16 ? 1 : 3)) || ((uintptr_t)mel & 3) || ((uintptr_t)fb & 3) || ((uintptr_t)fb_range & 3) ||
+      ((uintptr_t)basis & 3) || ((uintptr_t)n_samples & 3) || ((uintptr_t)n_valid & 3) || ((uintptr_t)scale & 3))
+    return L2S_EALIGN;
+  dim3 grid((unsigned)((T_rows + FT - 1) / FT), (unsigned)B), blk(256);
+  if (wav_is_i16)
+    hipLaunchKernelGGL(mel_power_kernel<true>, grid, blk, 0, (hipStream_t)stream, wav, ldw, n_samples, n_valid, scale, S, basis, fb, fb_range,
+                       mel, ldm, T_rows, pad);
+  else
+    hipLaunchKernelGGL(mel_power_kernel<false>, grid, blk, 0, (hipStream_t)stream, wav, ldw, n_samples, n_valid, scale, S, basis, fb, fb_range,
+                       mel, ldm, T_rows, pad);
+  L2S_CHECK_LAUNCH();
+  return L2S_OK;
+}
+
+extern "C" int l2s_spk_embed_head(const float* h_last, int n_rows, const int32_t* first, const int32_t* count, const float* w_t,
+                                  const float* bias, int B, int hidden, float* out, void* stream) {
+  if (!h_last || !first || !count || !w_t || !bias || !out) return L2S_EINVAL;
+  if (B <= 0 || n_rows <= 0 || hidden <= 0) return L2S_ESHAPE;
+  if (hidden != HID) return L2S_EUNSUPPORTED;
+  if (n_rows > (1 << 30)) return L2S_EUNSUPPORTED;
+  if (((uintptr_t)h_last | (uintptr_t)first | (uintptr_t)count | (uintptr_t)w_t | (uintptr_t)bias | (uintptr_t)out) & 3) return L2S_EALIGN;
+  hipLaunchKernelGGL(spk_head_kernel, dim3((unsigned)B), dim3(HID), 0, (hipStream_t)stream, h_last, n_rows, first, count, w_t, bias, out);
+  L2S_CHECK_LAUNCH();
+  return L2S_OK;
+}

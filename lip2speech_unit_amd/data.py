@@ -229,8 +229,11 @@ def audio_num_samples(path, pad=None):
 
 class MelCodeDataset:
     def __init__(self, file_list, code_hop_size=320, mel_hop_size=160, code_dict_path=None, pad=None, mel_from_audio=False,
-                 stft=None, segment_size=None, seed=1234, load_audio=False, sampling_rate=16000):
-        """mel_from_audio: the mel/ directory is not touched - the wav is read, zero-extended to the padded length and analysed
+                 stft=None, segment_size=None, seed=1234, load_audio=False, sampling_rate=16000, spk_embedder=None):
+        """spk_embedder (None: spk_emb/<name>.npy is read): a callable wav path -> float32 (256,), e.g.
+        speaker_encoder.SpeakerEncoder.embed_file - the embedding is computed from the clip's audio and spk_emb/ is not touched.
+
+        mel_from_audio: the mel/ directory is not touched - the wav is read, zero-extended to the padded length and analysed
         on the device (audio.TacotronSTFT, or `stft`: anything with its mel_rows) before the same trimming rule applies.
 
         segment_size (None: today's inference items, audio not read unless load_audio): the training / validation items of
@@ -253,6 +256,7 @@ class MelCodeDataset:
         self.rng, self.starts = random.Random(seed), {}
         self.code_dict = load_code_dict(code_dict_path)
         self.speaker_emb_files = [f.replace("/audio/", "/spk_emb/")[:-4] + ".npy" for f in self.audio_files]
+        self.spk_embedder = spk_embedder
 
     def __len__(self):
         return len(self.audio_files)
@@ -295,7 +299,8 @@ class MelCodeDataset:
             wav, code, mel, t_label = self._segment(index, filename, n_audio, cut, code, mel,
                                                     None if t_label is None else t_label[: cut // self.code_hop_size])
         feats = {"code": code.astype(np.int64), "mel": np.ascontiguousarray(mel).astype(np.float32),
-                 "spkr": np.load(self.speaker_emb_files[index]).astype(np.float32)}
+                 "spkr": (np.load(self.speaker_emb_files[index]) if self.spk_embedder is None
+                          else np.asarray(self.spk_embedder(filename))).astype(np.float32)}
         if t_label is not None:
             feats["t_label"] = t_label[: cut // self.code_hop_size] if wav is None else t_label
         return feats, wav, str(filename), None

@@ -913,6 +913,102 @@ def stoi_scores(bands, n_kept, seg, stoi, estoi, n_segments, *, B, ldf, lds=None
         nbytes=4.0 * B * 2 * 15 * ldf)
 
 
+def _wav_common(name, wav, n_samples, B, S, ldw):
+    if wav.dtype not in (torch.float32, torch.int16):
+        raise L2SError(f"wav: expected float32 or int16, got {wav.dtype}")
+    _req(wav, None, "wav")
+    if n_samples is not None:
+        _req(n_samples, torch.int32, "n_samples")
+        if n_samples.numel() < B:
+            raise L2SError(f"{name}: n_samples shorter than B")
+    if (B - 1) * ldw + S > _extent(wav):
+        raise L2SError(f"{name}: wav smaller than [B, S] of ldw")
+
+
+def wav_gain(wav, gain, *, B, S, n_samples=None, ldw=None, target_dbfs=-30.0):
+    """Per-clip volume factor of the speaker encoder (csrc/spkemb.hip): gain fp32 [B] = 10^(change/20) where
+    change = target_dbfs - 10 log10(mean(wav^2)) > 0, else 1 (increase only); wav fp32 or int16 [B, S], n_samples int32 [B]."""
+    ldw = ldw if ldw is not None else S
+    _wav_common("wav_gain", wav, n_samples, B, S, ldw)
+    _req(gain, torch.float32, "gain")
+    if gain.numel() < B:
+        raise L2SError("wav_gain: gain shorter than B")
+    _run("l2s_wav_gain", lambda: _lib.load().l2s_wav_gain(
+        _ptr(wav), int(wav.dtype == torch.int16), ldw, _ptr(n_samples), B, S, float(target_dbfs), _ptr(gain), _stream()),
+        nbytes=float(B) * S * wav.element_size())
+
+
+def stft_mel_power(wav, mel, basis, fb, fb_range, *, B, S, T_rows, n_samples=None, n_valid=None, scale=None, ldw=None, ldm=None,
+                   n_fft=400, hop=160, n_mels=40, pad=200):
+    """40-band power mel of 400-sample frames (csrc/spkemb.hip; speaker_encoder.PowerMel builds the tables): wav fp32 or int16
+    [B, S] -> mel fp32 [B, T_rows, n_mels], linear power.  n_samples: int32 [B] analysis lengths (frame count and reflection; may
+    exceed S), n_valid: int32 [B] real samples (zeros from there on, never read), scale: fp32 [B] per-clip factor."""
+    ldw = ldw if ldw is not None else S
+    ldm = ldm if ldm is not None else n_mels
+    _wav_common("stft_mel_power", wav, n_samples, B, S, ldw)
+    _req(mel, torch.float32, "mel"), _req(basis, torch.float32, "basis"), _req(fb, torch.float32, "fb"), _req(fb_range, torch.int32, "fb_range")
+    if n_valid is not None:
+        _req(n_valid, torch.int32, "n_valid")
+    if scale is not None:
+        _req(scale, torch.float32, "scale")
+    if any(t is not None and t.numel() < B for t in (n_valid, scale)):
+        raise L2SError("stft_mel_power: n_valid / scale shorter than B")
+    if ((B * T_rows - 1) * ldm + n_mels) > _extent(mel):
+        raise L2SError("stft_mel_power: mel smaller than [B, T_rows, ldm]")
+    if basis.numel() < n_fft * 448 or not basis.is_contiguous() or fb.numel() < n_mels * (n_fft // 2 + 1) or fb_range.numel() < 2 * n_mels:
+        raise L2SError("stft_mel_power: tables smaller than [n_fft, 448], [n_mels, n_fft/2 + 1], [n_mels, 2]")
+    frames = float(B) * T_rows
+    _run("l2s_stft_mel_power", lambda: _lib.load().l2s_stft_mel_power(
+        _ptr(wav), int(wav.dtype == torch.int16), ldw, _ptr(n_samples), _ptr(n_valid), _ptr(scale), B, S, _ptr(basis), _ptr(fb),
+        _ptr(fb_range), _ptr(mel), ldm, T_rows, n_fft, hop, n_mels, pad, _stream()),
+        flops=2.0 * frames * n_fft * 448, nbytes=float(B) * S * wav.element_size() + 4.0 * frames * n_mels + 4.0 * n_fft * 448)
+
+
+def lstm_layer(xproj, row_off, w_hh_p, *, S, T, n_rows=None, ldx=None, hidden=256, h_seq=None, h_last=None):
+    """One LSTM layer's recurrence (csrc/lstm.hip): xproj fp32 [n_rows, ldx] = x W_ih^T + b with gate-interleaved columns 4 u + g,
+    row_off int32 [S] (sequence s reads rows row_off[s] + t), w_hh_p fp32 [256, 256, 4] (speaker_encoder.pack_lstm_layer);
+    h_seq fp32 [S, T, 256] and / or h_last fp32 [S, 256]."""
+    _req(xproj, torch.float32, "xproj"), _req(row_off, torch.int32, "row_off"), _req(w_hh_p, torch.float32, "w_hh_p")
+    if xproj.dim() != 2:
+        raise L2SError("lstm_layer: xproj must be [n_rows, ldx]")
+    n_rows = n_rows if n_rows is not None else xproj.shape[0]
+    ldx = ldx if ldx is not None else xproj.stride(0)
+    if (n_rows - 1) * ldx + 4 * hidden > _extent(xproj) or row_off.numel() < S or not row_off.is_contiguous():
+        raise L2SError("lstm_layer: xproj smaller than [n_rows, 4 hidden] of ldx or row_off shorter than S")
+    if not w_hh_p.is_contiguous() or w_hh_p.numel() < 4 * hidden * hidden:
+        raise L2SError("lstm_layer: w_hh_p must be dense [hidden, hidden, 4]")
+    if h_seq is None and h_last is None:
+        raise L2SError("lstm_layer: h_seq or h_last is needed")
+    if h_seq is not None:
+        _req(h_seq, torch.float32, "h_seq")
+        if not h_seq.is_contiguous() or h_seq.numel() < S * T * hidden:
+            raise L2SError("lstm_layer: h_seq must be dense [S, T, hidden]")
+    if h_last is not None:
+        _req(h_last, torch.float32, "h_last")
+        if not h_last.is_contiguous() or h_last.numel() < S * hidden:
+            raise L2SError("lstm_layer: h_last must be dense [S, hidden]")
+    _run("l2s_lstm_layer", lambda: _lib.load().l2s_lstm_layer(
+        _ptr(xproj), ldx, n_rows, _ptr(row_off), _ptr(w_hh_p), S, T, hidden, _ptr(h_seq), _ptr(h_last), _stream()),
+        flops=2.0 * S * T * hidden * 4 * hidden, nbytes=4.0 * S * T * (4 * hidden + (hidden if h_seq is not None else 0)),
+        shape=f"S{S} T{T}")
+
+
+def spk_embed_head(h_last, first, count, w_t, bias, out, *, B, n_rows=None, hidden=256):
+    """The speaker encoder's head (csrc/spkemb.hip): per clip b over h_last rows [first[b], first[b] + count[b]): relu(W h + bias),
+    / (norm + 1e-5), mean in index order, / norm -> out fp32 [B, 256].  w_t fp32 [256, 256] = linear.weight transposed."""
+    for t, n in ((h_last, "h_last"), (w_t, "w_t"), (bias, "bias"), (out, "out")):
+        _req(t, torch.float32, n)
+    _req(first, torch.int32, "first"), _req(count, torch.int32, "count")
+    n_rows = n_rows if n_rows is not None else h_last.shape[0]
+    if not h_last.is_contiguous() or h_last.numel() < n_rows * hidden or not w_t.is_contiguous() or w_t.numel() < hidden * hidden:
+        raise L2SError("spk_embed_head: h_last must be dense [n_rows, hidden] and w_t dense [hidden, hidden]")
+    if bias.numel() < hidden or min(first.numel(), count.numel()) < B or not out.is_contiguous() or out.numel() < B * hidden:
+        raise L2SError("spk_embed_head: bias [hidden], first / count [B], out dense [B, hidden]")
+    _run("l2s_spk_embed_head", lambda: _lib.load().l2s_spk_embed_head(
+        _ptr(h_last), n_rows, _ptr(first), _ptr(count), _ptr(w_t), _ptr(bias), B, hidden, _ptr(out), _stream()),
+        flops=2.0 * n_rows * hidden * hidden, nbytes=4.0 * (n_rows + B + hidden) * hidden)
+
+
 # ---- torch.library registration ("PyTorch-ROCm custom ops", SURVEY 8b last row) --------------------------------------------------
 # Every launcher above is ALSO a dispatcher-visible operator `torch.ops.lip2speech.<name>` (schema below, CUDA = HIP kernel only: a
 # CPU tensor finds no kernel and raises; a fake / meta implementation gives shapes to torch.compile and fake-tensor tracing), and
@@ -1026,6 +1122,14 @@ _SCHEMAS = {
                   "int B, int S, int ldf, Tensor? n_samples=None, int? ldx=None, int? ldk=None) -> ()",
     "stoi_scores": "(Tensor bands, Tensor n_kept, Tensor(a!) seg, Tensor(b!) stoi, Tensor(c!) estoi, Tensor(d!) n_segments, *, int B, "
                    "int ldf, int? lds=None) -> ()",
+    "wav_gain": "(Tensor wav, Tensor(a!) gain, *, int B, int S, Tensor? n_samples=None, int? ldw=None, float target_dbfs=-30.0) -> ()",
+    "stft_mel_power": "(Tensor wav, Tensor(a!) mel, Tensor basis, Tensor fb, Tensor fb_range, *, int B, int S, int T_rows, "
+                      "Tensor? n_samples=None, Tensor? n_valid=None, Tensor? scale=None, int? ldw=None, int? ldm=None, int n_fft=400, "
+                      "int hop=160, int n_mels=40, int pad=200) -> ()",
+    "lstm_layer": "(Tensor xproj, Tensor row_off, Tensor w_hh_p, *, int S, int T, int? n_rows=None, int? ldx=None, int hidden=256, "
+                  "Tensor(a!)? h_seq=None, Tensor(b!)? h_last=None) -> ()",
+    "spk_embed_head": "(Tensor h_last, Tensor first, Tensor count, Tensor w_t, Tensor bias, Tensor(a!) out, *, int B, "
+                      "int? n_rows=None, int hidden=256) -> ()",
 }
 # C-ABI entry each operator launches (tests/test_torchlib_cpu.py: every device entry of include/lip2speech_hip.h has a twin)
 ENTRY_OF = {n: "l2s_" + n for n in _SCHEMAS}

@@ -4,9 +4,13 @@
   python -m lip2speech_unit_amd.vocoder_inference <config.json> <label/test.tsv> <dict.unt.txt> \
       --output_dir D --checkpoint_file C -n -1 [--pad N] [--synthetic_weights] [--mel_from_audio]
       [--units_from_audio --hubert <ckpt> --kmeans <km.bin|centers.npy> [--units_layer 6] [--units_dtype f32|f16|bf16]] [--stoi]
+      [--spk_emb_from_audio --speaker_encoder <encoder.pt>]
 --mel_from_audio: the mel conditioning is analysed from audio/*.wav on the device (audio.TacotronSTFT); mel/ is not read.
 --units_from_audio: the units are computed from audio/*.wav on the device (speech_units.SpeechUnitExtractor); the .unt file is
 not read.  With both flags stage 2 runs from a folder of wavs and speaker embeddings alone.
+--spk_emb_from_audio (off by default): the speaker embedding is computed from audio/*.wav on the device
+(speaker_encoder.SpeakerEncoder; with --synthetic_weights its build-owned weights); spk_emb/ is not read.  With all three flags
+stage 2 runs from a folder of wavs alone.
 Writes D/pred_wav/<spk>/<utt>.wav (int16, 16 kHz) like :157-165.
 --stoi (off by default): the clips just written are scored against the manifest's audio on the device (evaluate.report: STOI and
 ESTOI, the summary line and D/eval-stoi.json).
@@ -57,6 +61,8 @@ def build_parser():
     p.add_argument("--units_layer", type=int, default=6)
     p.add_argument("--units_dtype", default="f32", choices=["f32", "f16", "bf16"])
     p.add_argument("--stoi", action="store_true", default=argparse.SUPPRESS)   # absent: the namespace is what it was without the flag
+    p.add_argument("--spk_emb_from_audio", action="store_true", default=argparse.SUPPRESS)   # absent likewise, and so is the next
+    p.add_argument("--speaker_encoder", default=argparse.SUPPRESS)
     return p
 
 
@@ -65,6 +71,9 @@ def main(argv=None):
     a = p.parse_args(argv)
     if a.units_from_audio and not (a.hubert and a.kmeans):
         p.error("--units_from_audio needs --hubert and --kmeans")
+    spk_from_audio = getattr(a, "spk_emb_from_audio", False)
+    if spk_from_audio and not (a.synthetic_weights or getattr(a, "speaker_encoder", None)):
+        p.error("--spk_emb_from_audio needs --speaker_encoder (or --synthetic_weights)")
     if a.code_file is not None:
         raise NotImplementedError("--code_file (units without mel/speaker) is not the multi-input path")
     if not torch.cuda.is_available():
@@ -89,8 +98,17 @@ def main(argv=None):
         file_list = manifest_from_audio(a.input_code_file, extractor)
     else:
         file_list = parse_manifest(a.input_code_file)
+    ds_kw = {}
+    if spk_from_audio:
+        from . import speaker_encoder
+        enc = speaker_encoder.SpeakerEncoder()
+        if a.synthetic_weights:
+            enc.load_state_dict(speaker_encoder.synthetic_state_dict())
+        else:
+            enc.load_checkpoint(a.speaker_encoder)
+        ds_kw["spk_embedder"] = enc.eval().embed_file
     ds = MelCodeDataset(file_list, h.code_hop_size, h.mel_hop_size, code_dict_path=a.code_dict_path,
-                        pad=a.pad, mel_from_audio=a.mel_from_audio)
+                        pad=a.pad, mel_from_audio=a.mel_from_audio, **ds_kw)
     os.makedirs(a.output_dir, exist_ok=True)
     n = len(ds) if a.n == -1 else min(a.n, len(ds))
     audio_s, wall = 0.0, 0.0
