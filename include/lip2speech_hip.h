@@ -345,7 +345,9 @@ int l2s_split_hi_lo(const float* x, int ldx, void* hi, void* lo, int ld16, int a
 
 /*
  * Fused convolution PAIR of ResBlock1 for the wide vocoder stages (speech-resynthesis/models.py:34-41, one (c1, c2, d) step):
- *   x' = c2(leaky_relu(c1(leaky_relu(x)))) + x,  C in {64, 128}, k odd <= 11, (k-1)/2 * dil <= 32.
+ *   x' = c2(leaky_relu(c1(leaky_relu(x)))) + x,  C in {64, 128, 256}, k odd <= 17, h1 = (k-1)/2 * dil <= 28 (C = 256) or <= 32
+ *   (C = 64 / 128: h1 = 29 .. 32 runs on the 192-row kernels of csrc/respair.hip, l2s_respair_variant says which); other shapes
+ *   answer L2S_EUNSUPPORTED.  tests/test_vocconv_matrix_gpu.py runs every kernel at these limits.
  * The pair's input and output travel as their LeakyReLU'd 16-bit copies only (x is recovered by the inverse of leaky_relu);
  * the intermediate never leaves LDS.  X: [B*T, C] = leaky_relu(x), rows t >= lens[b]*len_mul zero; W1 / W2: [C][k*C] 16-bit,
  * K = tap*C + c (W1 applied with dilation dil, W2 with dilation 1, both "same" padded); b1 / b2: [C] fp32.
@@ -353,7 +355,8 @@ int l2s_split_hi_lo(const float* x, int ldx, void* hi, void* lo, int ld16, int a
  * accumulate: the sum over the stage's ResBlocks, models.py:103-108) and, when Y is given, Y = leaky_relu(XS).
  * last == 2 (the stage's final pair when only Y travels on: `x = xs / num_kernels` feeds leaky_relu + ups, models.py:109,101):
  * XS is read for the sum but NOT written back - Y = leaky_relu(XS + x') is the only output.
- * Rows at or past the clip length are written as zero.
+ * Rows at or past the clip length are written as zero, in Y and in XS, whatever XS held there before an accumulating launch.
+ * lens == NULL: every clip has T rows.
  */
 typedef struct l2s_respair_desc {
   const void* X; const void* W1; const void* W2; const float* b1; const float* b2;
@@ -362,12 +365,16 @@ typedef struct l2s_respair_desc {
   float slope;
 } l2s_respair_desc;
 int l2s_respair(const l2s_respair_desc* d, void* stream);
+/* l2s_respair_variant (host-only, as l2s_attention_variant: nothing is launched, no pointer is dereferenced, pointers count for the
+ * null and alignment checks only): RM * 1000 + C of the kernel l2s_respair would run for d, RM = the rows a tile computes -
+ * 192064 / 192128: csrc/respair.hip; 512064 / 256128 / 128256: csrc/respair_phase.hip - or the error code of the launch. */
+int l2s_respair_variant(const l2s_respair_desc* d);
 
 /*
  * The LAST conv pairs of a stage's n <= 3 ResBlocks in one launch (speech-resynthesis/models.py:103-109 over :34-41):
  *   Y [B*T, C] = leaky_relu( sum_j ( c2_j(leaky_relu(c1_j(leaky_relu(x_j)))) + x_j ) ),  C in {64, 128, 256}
  * where X[j] = leaky_relu(x_j) is the input of ResBlock j's last (c1, c2, d) pair - what l2s_respair(last = 0) of its previous pair
- * wrote.  Same operand layouts and limits as l2s_respair (k odd <= 11, (k-1)/2 * dil <= 28).  The stage's fp32 sum is kept in
+ * wrote.  Same operand layouts and limits as l2s_respair (k odd <= 17, (k-1)/2 * dil <= 28).  The stage's fp32 sum is kept in
  * accumulators across the ResBlocks and never written: use it where only leaky_relu of the sum travels on (`x = xs / num_kernels`
  * feeds leaky_relu + ups, models.py:109,101 - every stage but the last); results equal n l2s_respair(last != 0) launches up to the
  * order of the fp32 additions.  Rows at or past the clip length are written as zero.
@@ -418,6 +425,9 @@ int l2s_basicstage128_tail_fused(const void* x0, const void* t0, const void* wa,
  * Vocoder tail: leaky_relu(x, 0.01) -> Conv1d(C->1, k7, p3) -> tanh -> *32768 -> int16 truncation.
  * speech-resynthesis/models.py:110-112 ; multi_input_vocoder/inference.py:79-81.
  * x: [B*T, C] fp32 (sum of the three ResBlocks; the /3 is folded into w); w: [k, C] fp32; wav: [B, T] fp32; pcm: [B, T] int16 or NULL.
+ * k odd, (256 + k - 1) (C + 1) + k C floats of LDS <= 64 KB (else L2S_EUNSUPPORTED).  Samples at or past the clip length are zero.
+ * A saturated sample - tanh returns exactly +-1.0f for a pre-activation beyond about +-9 - has wav * 32768 = +-32768: pcm is
+ * -32768 for both signs, what numpy's astype('int16') of the reference gives (+32768 wraps).
  */
 int l2s_conv_post_tanh(const float* x, const float* w, float bias, float* wav, int16_t* pcm, const int32_t* lens,
                        int len_mul, int B, int T, int C, int k, void* stream);
@@ -428,7 +438,11 @@ int l2s_conv_post_tanh(const float* x, const float* w, float bias, float* wav, i
  * the block output into xs (the sum over the stage's three ResBlocks, models.py:103-108).
  * xl: [B*T, C] 16-bit; w: [6][C][Kpad] 16-bit in the order c1(d0),c2,c1(d1),c2,c1(d2),c2 with K = tap*C + c zero-padded to
  * a multiple of 32; bias: [6][C] fp32; xs: [B*T, C] fp32 (overwritten, or added to when accumulate != 0);
- * xl_out (optional): [B*T, C] 16-bit = leaky_relu(xs after this call).  Rows t >= lens[b]*len_mul are zero.
+ * xl_out (optional, 8-byte aligned): [B*T, C] 16-bit = leaky_relu(xs after this call).  Rows t >= lens[b]*len_mul are never read
+ * from xl and the ResBlock's output is zero there: xs is written as zero when accumulate == 0 and keeps its previous content when
+ * accumulate != 0 (0 + xs; a stage's sum starts with an overwriting launch and stays zero there), xl_out is leaky_relu of that.
+ * Dilations 1 .. 5 each.  The time tile with its halo of (k-1)/2 * (d0 + d1 + d2 + 3) rows has to fit 160 KB of LDS: that is every
+ * set but d0 + d1 + d2 > 11 at C = 32, k = 11, which answers L2S_EUNSUPPORTED (the generator's set is (1, 3, 5)).
  */
 int l2s_resblock_fused(const void* xl, const void* w, const float* bias, float* xs, void* xl_out,
                        const int32_t* lens, int len_mul, int B, int T, int C, int k, int d0, int d1, int d2,
@@ -446,7 +460,8 @@ int l2s_resblock_fused(const void* xl, const void* w, const float* bias, float* 
  * xs_final != 0: xs holds the stage's sum afterwards (conv_post reads it); xs_final == 0 (xl_out required): only
  * leaky_relu(sum) is written and xs is scratch (content afterwards unspecified; ABI 14 - up to ABI 13 it held the partial
  * sum after the second ResBlock).
- * Other stage layouts return L2S_EUNSUPPORTED (the caller launches the ResBlocks one by one).
+ * Other stage layouts return L2S_EUNSUPPORTED (the caller launches the ResBlocks one by one); so do, at C = 32, dilation sets
+ * whose tile does not fit the LDS: d0 + d1 + d2 > 13 for k = 7 or > 9 for k = 11 (the generator's (1, 3, 5) fits).
  */
 int l2s_resstage_fused(const void* xl, const void* const* w, const float* const* bias, const int* ks, const int* dils,
                        int n_blocks, float* xs, void* xl_out, const int32_t* lens, int len_mul, int B, int T, int C,

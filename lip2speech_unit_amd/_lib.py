@@ -107,6 +107,7 @@ SIGNATURES = {
     "l2s_resblock_fused": ([_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _f, _i, _vp], _i),
     "l2s_resstage_fused": ([_vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _i, _i, _i, _i, _f, _i, _i, _vp], _i),
     "l2s_respair": ([ctypes.POINTER(RespairDesc), _vp], _i),
+    "l2s_respair_variant": ([ctypes.POINTER(RespairDesc)], _i),
     "l2s_respair_final": ([ctypes.POINTER(RespairFinalDesc), _vp], _i),
     "l2s_preprocess_frames": ([_vp, _vp, _i, _i, _i, _i, _i, _f, _f, _i, _vp], _i),
     "l2s_mel_spectrogram": ([_vp, _i, ctypes.c_int64, _vp, _i, _i, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _f, _vp], _i),

@@ -186,6 +186,12 @@ __global__ void split_hi_lo_kernel(const float* __restrict__ x, int ldx, uint16_
 
 // speech-resynthesis/models.py:110-112 + multi_input_vocoder/inference.py:79-81
 constexpr int CP_TILE = 256;
+// astype('int16') of o * 32768: truncation toward zero.  |o| <= 1, and tanhf does return exactly +-1.0f (|x| > 9): 32768 is
+// out of int16's range, where numpy wraps to -32768 (the conversion goes through int32).  Through int here as well, the wrap spelled out.
+__device__ __forceinline__ int16_t pcm_of(float o) {
+  const int q = (int)(o * 32768.0f);               // |q| <= 32768
+  return (int16_t)(q > 32767 ? q - 65536 : q);
+}
 __global__ __launch_bounds__(256) void conv_post_kernel(const float* __restrict__ x, const float* __restrict__ w,
                                                         float bias, float* __restrict__ wav, int16_t* __restrict__ pcm,
                                                         const int32_t* __restrict__ lens, int len_mul, int T, int C,
@@ -218,7 +224,7 @@ __global__ __launch_bounds__(256) void conv_post_kernel(const float* __restrict_
   float o = tanhf(acc);
   if (t >= lim) o = 0.f;
   wav[(int64_t)b * T + t] = o;
-  if (pcm) pcm[(int64_t)b * T + t] = (int16_t)(o * 32768.0f);  // astype('int16'): truncation toward zero, |o| < 1
+  if (pcm) pcm[(int64_t)b * T + t] = pcm_of(o);
 }
 
 // The generator's own shape (upsample_initial_channel / 2^5 = 16 channels, conv_post kernel 7): the 1 KB-per-16-samples input
@@ -262,7 +268,7 @@ __global__ __launch_bounds__(256) void conv_post16_kernel(const float* __restric
   float o = tanhf(acc);
   if (t >= lim) o = 0.f;
   wav[(int64_t)b * T + t] = o;
-  if (pcm) pcm[(int64_t)b * T + t] = (int16_t)(o * 32768.0f);  // astype('int16'): truncation toward zero, |o| < 1
+  if (pcm) pcm[(int64_t)b * T + t] = pcm_of(o);
 }
 
 }  // namespace

@@ -70,7 +70,7 @@ template <int C, int K> struct RSCfg {
   static constexpr int NW = C == 32 ? 8 : 4;
   static constexpr int BPC = C == 16 ? 3 : 1;
   static constexpr int WPE = (BPC * NW + 3) / 4;
-  static constexpr int TLB = C == 16 ? 4 : 6;    // covers the whole tile for every legal dilation set (RB <= 768 rows)
+  static constexpr int TLB = C == 16 ? 4 : 6;    // C = 32 covers the whole tile (RB <= 768 rows x 4 chunks); C = 16 needs a second batch past 512 rows
   template <int KK> static constexpr bool wb2() { return KK != 11; }
 };
 // 16-row groups per pipeline stage: two at C = 16 (NI = 1) so that two MFMA chains are in flight; k = 11 keeps one (two

@@ -4,7 +4,7 @@
 // As two tap-GEMM launches a pair moves six activation arrays through HBM (c1: read lrelu(x), write t1; c2: read t1, read
 // x, write x', write lrelu(x')) and the C = 64 / 128 second convolutions ran at 3-4.8 TB/s of algorithmic traffic: HBM-bound
 // by construction.  Here one block owns a tile of 192 time steps of one clip and HBM sees TWO arrays:
-//   * the input is the LeakyReLU'd copy only: patch rows (192 + 2*h1 halo, h1 = (k-1)/2*dil <= 25) arrive by LDS-DMA; the raw
+//   * the input is the LeakyReLU'd copy only: patch rows (192 + 2*h1 halo, h1 = (k-1)/2*dil <= 32) arrive by LDS-DMA; the raw
 //     x of the residual is recovered from it by the inverse of leaky_relu (x = xl >= 0 ? xl : xl / slope), as resblock.hip does;
 //   * conv1 runs on MFMA out of the patch (tap = row shift), its bias + LeakyReLU + length mask are applied in the MFMA
 //     register layout and t1 goes back into the SAME LDS region as 16-bit rows (the patch is dead by then; the residual
@@ -24,11 +24,13 @@
 using namespace l2s;
 using l2s_rp::RpArgs;
 
+int l2s_respair_grid(int ntiles, int slots);   // below: the pair kernels' grid, with the L2S_RESPAIR_SLOTS cap
+
 namespace {
 
 constexpr int RM = 192;       // rows both convolutions compute per tile
-constexpr int RPR = 256;      // rows of LDS region A: the patch (RM + 2*h1 <= 242 rows), later t1 (rows 8 .. 8+RM)
-constexpr int T1_ROW0 = 8;    // t1 row p lives at region row p + 8: conv2's taps reach rows p - h2 >= -5
+constexpr int RPR = 256;      // rows of LDS region A: the patch (RM + 2*h1 <= 256 rows: h1 <= 32), later t1 (rows 8 .. 8+RM)
+constexpr int T1_ROW0 = 8;    // t1 row p lives at region row p + 8: conv2's taps reach rows p - h2 >= -8 (k <= 17)
 constexpr int RQ = 4;         // weight ring slots
 constexpr int rp_smem(int ch) { return (ch / 64) * RPR * 128 + RQ * ch * 128 + (ch / 16) * 4096; }   // 80 KB / 160 KB
 
@@ -290,8 +292,8 @@ __global__ __launch_bounds__(CH * 4, (CH == 64 ? 2 : 1)) void respair_kernel(con
 #pragma unroll
         for (int j = 0; j < NI; ++j) {
           f32x4_t v = acc[i][j] + b2j[j];
-          if (!keep) v = f32x4_t{0.f, 0.f, 0.f, 0.f};
           v = v + old[i][j];
+          if (!keep) v = f32x4_t{0.f, 0.f, 0.f, 0.f};   // rows at or past the clip length are WRITTEN as zero, whatever XS held
           if (o >= 0) {
             if (a.write_xs) *reinterpret_cast<float4*>(xs + j * 16) = make_float4(v[0], v[1], v[2], v[3]);
             if (a.Y) {
@@ -318,8 +320,7 @@ int launch_respair(const RpArgs& a, hipStream_t st) {
   static L2sSmemOptIn opt_in;  // > 64 KB of dynamic LDS: opt-in per instantiation and device
   if (int e = l2s_smem_opt_in(kern, SMEM, opt_in)) return e;
   constexpr int slots = CH == 64 ? 512 : 256;   // resident blocks: two per CU at 64 channels, one at 128
-  const int need = (a.ntiles + 7) & ~7;         // a multiple of 8: every XCD group has the same number of blocks
-  const int grid = need < slots ? need : slots;
+  const int grid = l2s_respair_grid(a.ntiles, slots);
   hipLaunchKernelGGL(kern, dim3(grid), dim3(CH * 4), SMEM, st, a);
   L2S_CHECK_LAUNCH();
   return L2S_OK;
@@ -332,13 +333,29 @@ int l2s_respair_phase_rows(int C);
 bool l2s_respair_phase_supports(int C, int h1, int h2);
 int l2s_respair_phase_launch(const RpArgs& a, int C, int dtype, int kind, hipStream_t st);
 
-extern "C" int l2s_respair(const l2s_respair_desc* d, void* stream) {
+// Grid of the pair kernels (this file's, respair_phase.hip's and respair_final): the tiles rounded up to a multiple of 8 (every XCD
+// group has the same number of blocks), at most `slots` resident blocks.  L2S_RESPAIR_SLOTS = n >= 8 (read once per process; unset
+// or 0: nothing changes) caps it at n rounded down to a multiple of 8, so that a test makes a block walk many tiles of a small batch.
+int l2s_respair_grid(int ntiles, int slots) {
+  static const int cap = [] { const char* e = getenv("L2S_RESPAIR_SLOTS"); const int n = e ? atoi(e) : 0; return n >= 8 ? n & ~7 : 0; }();
+  const int need = (ntiles + 7) & ~7;
+  int grid = need < slots ? need : slots;
+  if (cap && grid > cap) grid = cap;
+  return grid;
+}
+
+namespace {
+
+// Which kernel l2s_respair runs for d (the launch and l2s_respair_variant both ask here): RM * 1000 + C on success - RM = 192: this
+// file's kernels, else respair_phase.hip's - or the negative error code.  Host only: pointers count for null checks and alignment.
+int respair_select(const l2s_respair_desc* d) {
   if (!d || !d->X || !d->W1 || !d->W2 || !d->b1 || !d->b2) return L2S_EINVAL;
   if (d->last < 0 || d->last > 2 || (d->last ? !d->XS : !d->Y)) return L2S_EINVAL;
   if (d->last == 2 && !d->Y) return L2S_EINVAL;     // XS read, not written: Y is the only output
   if (d->B <= 0 || d->T <= 0 || d->k < 1 || !(d->k & 1) || d->dil < 1) return L2S_ESHAPE;
   if (d->C != 64 && d->C != 128 && d->C != 256) return L2S_EUNSUPPORTED;
-  const int h2 = (d->k - 1) / 2, h1 = h2 * d->dil;
+  const int h2 = (d->k - 1) / 2;
+  const int h1 = (int64_t)h2 * d->dil > 1000 ? 1000 : h2 * d->dil;   // (clamped: no such halo fits, and the product cannot overflow)
   // C = 256 always, C = 128 / 64 by default run on the phase-staggered kernel of respair_phase.hip; L2S_RESPAIR_PHASE is a bit
   // mask (1: C = 128, 2: C = 64; 0 = this file's 192-row kernels, the A/B reference)
   static const int phase128 = [] { const char* e = getenv("L2S_RESPAIR_PHASE"); return e ? atoi(e) : 3; }();
@@ -351,6 +368,21 @@ extern "C" int l2s_respair(const l2s_respair_desc* d, void* stream) {
       ((uintptr_t)d->XS & 15) || ((uintptr_t)d->b1 & 15) || ((uintptr_t)d->b2 & 15))
     return L2S_EALIGN;
   if ((int64_t)d->B * d->T >= ((int64_t)1 << 31) / 2) return L2S_EUNSUPPORTED;   // 32-bit row math in the epilogue
+  if (d->dtype != L2S_F16 && d->dtype != L2S_BF16) return L2S_EINVAL;
+  return rm * 1000 + d->C;
+}
+
+}  // namespace
+
+/* include/lip2speech_hip.h: l2s_respair_variant */
+extern "C" int l2s_respair_variant(const l2s_respair_desc* d) { return respair_select(d); }
+
+extern "C" int l2s_respair(const l2s_respair_desc* d, void* stream) {
+  const int variant = respair_select(d);
+  if (variant < 0) return variant;
+  const int h2 = (d->k - 1) / 2, h1 = h2 * d->dil;
+  const int rm = variant / 1000;
+  const bool c256 = rm != RM;
   RpArgs a;
   a.X = (const uint16_t*)d->X; a.W1 = (const uint16_t*)d->W1; a.W2 = (const uint16_t*)d->W2;
   a.b1 = d->b1; a.b2 = d->b2; a.Y = (uint16_t*)d->Y; a.XS = d->XS; a.lens = d->lens;

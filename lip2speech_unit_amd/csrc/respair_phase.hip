@@ -6,7 +6,7 @@
 // launches that moved t1, x, x' and leaky_relu(x') through HBM and re-read every input row once per tap (PMC: 2.6 x the
 // algorithmic bytes on the first convolutions).  This kernel is respair's data flow on the phase-staggered schedule of
 // phasegemm_kernel.h:
-//   * one block owns 128 time steps of one clip x all 256 channels: the patch (128 + 2*h1 <= 178 rows of the LeakyReLU'd
+//   * one block owns 128 time steps of one clip x all 256 channels: the patch (128 + 2*h1 <= 184 rows of the LeakyReLU'd
 //     input, four 64-channel blocks of 184 x 128 B = 92 KB) arrives by LDS-DMA; conv1 runs out of it (tap = row shift), t1 goes
 //     back into the same region as 16-bit rows, conv2 runs out of t1; HBM sees the pair's input once (+ the halo) and its output
 //     once, the raw x of the residual is recovered from the LeakyReLU'd copy by the inverse of leaky_relu;
@@ -31,9 +31,11 @@
 using namespace l2s;
 using l2s_rp::RpArgs;
 
+int l2s_respair_grid(int ntiles, int slots);   // respair.hip: the pair kernels' grid, with the L2S_RESPAIR_SLOTS cap
+
 namespace {
 
-constexpr int XT1 = 8;                       // t1 row p lives at region row p + 8: conv2's taps reach rows p - h2 >= -5
+constexpr int XT1 = 8;                       // t1 row p lives at region row p + 8: conv2's taps reach rows p - h2 >= -8 (k <= 17)
 constexpr int XRQ = 4;                       // quarter slots
 // Geometry per channel count.  8 waves of 64 x 64: CH / 64 wave columns, the rest wave rows; the tile is as tall as the wave rows.
 //   CH = 256: 2 x 4 waves, 128-row tiles, region 4 x 184 rows (92 KB), 16 KB quarters (2 DMA instructions per wave and phase)
@@ -44,7 +46,7 @@ template <int CH>
 struct XGeo {
   static constexpr int NWC = CH / 64, NWR = 8 / NWC, NBLK = CH / 64;
   static constexpr int RM = NWR * 64;              // rows both convolutions compute per tile
-  static constexpr int RPR = RM + 56;              // rows of a region block: the patch (RM + 2*h1 <= RM + 50), later t1 (rows 8 .. 8+RM)
+  static constexpr int RPR = RM + 56;              // rows of a region block: the patch (RM + 2*h1 <= RM + 56: h1 <= 28), later t1 (rows 8 .. 8+RM+h2)
   static constexpr int BLK_B = RPR * 128;          // one 64-channel block of the region
   static constexpr int REGION = NBLK * BLK_B;
   static constexpr int QROWS = NWC * 32;           // weight rows of a quarter: 32 per wave column
@@ -432,8 +434,8 @@ __global__ __launch_bounds__(512) void respair_phase_kernel(const RpArgs a) {
 #pragma unroll
           for (int j = 0; j < NI; ++j) {
             f32x4_t v = acc[i][j];                             // b2 already inside
-            if (!keep) v = f32x4_t{0.f, 0.f, 0.f, 0.f};
             v = v + old[g2][j];
+            if (!keep) v = f32x4_t{0.f, 0.f, 0.f, 0.f};        // rows at or past the clip length are WRITTEN as zero, whatever XS held
             if (o >= 0) {
               if (a.write_xs) *reinterpret_cast<float4*>(xs + j * 16) = make_float4(v[0], v[1], v[2], v[3]);
               if (a.Y) {
@@ -586,8 +588,7 @@ int launch_respair_final(const l2s_rp::RpFinalArgs& a, hipStream_t st) {
   auto kern = respair_final_kernel<ET, CH>;
   static L2sSmemOptIn opt_in;
   if (int e = l2s_smem_opt_in(kern, SMEM, opt_in)) return e;
-  const int need = (a.ntiles + 7) & ~7;
-  const int grid = need < 256 ? need : 256;
+  const int grid = l2s_respair_grid(a.ntiles, 256);
   hipLaunchKernelGGL(kern, dim3(grid), dim3(512), SMEM, st, a);
   L2S_CHECK_LAUNCH();
   return L2S_OK;
@@ -599,8 +600,7 @@ int launch_respair_phase(const RpArgs& a, hipStream_t st) {
   auto kern = respair_phase_kernel<ET, CH, KIND>;
   static L2sSmemOptIn opt_in;  // > 64 KB of dynamic LDS: opt-in per instantiation and device
   if (int e = l2s_smem_opt_in(kern, G::SMEM, opt_in)) return e;
-  const int need = (a.ntiles + 7) & ~7;         // a multiple of 8: every XCD group has the same number of blocks
-  const int grid = need < 256 ? need : 256;     // one resident block per CU
+  const int grid = l2s_respair_grid(a.ntiles, 256);   // a multiple of 8 (every XCD group has the same number of blocks), one resident block per CU
   hipLaunchKernelGGL(kern, dim3(grid), dim3(512), G::SMEM, st, a);
   L2S_CHECK_LAUNCH();
   return L2S_OK;

@@ -510,6 +510,20 @@ def respair(x_l, w1, b1, w2, b2, *, B, T, C, k, dil, slope, y=None, xs=None, acc
          flops=2.0 * B * T * C * C * k * 2, nbytes=float(B) * T * C * arrays + 2.0 * 2 * C * C * k, shape=f"M{B * T} k{k}")
 
 
+def respair_variant(*, B, T, C, k, dil, slope=0.1, last=0, accumulate=False, lens=True, len_mul=1, dtype=F16):
+    """Host-only: RM * 1000 + C of the kernel l2s_respair would run (192064 / 192128: csrc/respair.hip; 512064 / 256128 / 128256:
+    csrc/respair_phase.hip), or its negative error code.  Needs no device and no tensors: the operands count as present and aligned."""
+    d = _lib.RespairDesc()
+    fake = 0x10000
+    d.X = d.W1 = d.W2 = d.b1 = d.b2 = fake
+    d.Y = fake if last != 1 else None
+    d.XS = fake if last else None
+    d.lens = fake if lens else None
+    d.len_mul, d.B, d.T, d.C, d.k, d.dil = len_mul, B, T, C, k, dil
+    d.last, d.accumulate, d.dtype, d.slope = last, int(bool(accumulate)), dtype, float(slope)
+    return _lib.load().l2s_respair_variant(ctypes.byref(d))
+
+
 def respair_final(xs_l, w1s, b1s, w2s, b2s, y, *, B, T, C, ks, dils, slope, lens=None, len_mul=1, dtype=F16):
     """The last conv pairs of a stage's ResBlocks in one launch (csrc/respair_phase.hip: respair_final_kernel):
     y = leaky_relu(sum_j (c2_j(leaky_relu(c1_j(x_l[j]))) + x_j)); the stage's fp32 sum stays in accumulators.  xs_l / w1s / b1s /
@@ -1135,7 +1149,7 @@ _SCHEMAS = {
 ENTRY_OF = {n: "l2s_" + n for n in _SCHEMAS}
 ENTRY_OF.update({"maxpool2d_3x3s2": "l2s_maxpool2d_3x3s2", "avgpool_hw": "l2s_avgpool_hw"})
 # host-side queries of the ABI (no launch, nothing for the dispatcher to see)
-HOST_QUERIES = ("l2s_abi_version", "l2s_build_info", "l2s_tapgemm_variant", "l2s_tapgemm_epilogue_family", "l2s_attention_variant", "l2s_layernorm_variant",
+HOST_QUERIES = ("l2s_abi_version", "l2s_build_info", "l2s_tapgemm_variant", "l2s_tapgemm_epilogue_family", "l2s_attention_variant", "l2s_layernorm_variant", "l2s_respair_variant",
                 "l2s_glu_dwconv_tile", "l2s_beam_decode_workspace",
                 "l2s_ctc_beam_workspace", "l2s_ctc_loss_workspace", "l2s_wave_stem_workspace", "l2s_kmeans_nearest_workspace",
                 "l2s_kmeans_update_workspace", "l2s_kmeans_pp_workspace")
