@@ -505,7 +505,7 @@ int l2s_mel_spectrogram(const void* wav, int wav_is_i16, int64_t ldw, const int3
  *   pad: reflect padding on each side, 0 <= pad <= n_fft/2.  Frame t of clip b covers samples [t*hop - pad, t*hop - pad + n_fft),
  *     reflected against the clip's own n_b; T_b = (n_b + 2 pad - n_fft) / hop + 1 frames when n_b > pad and n_b + 2 pad >= n_fft,
  *     else 0 (no valid reflection, or not one whole frame); rows T_b <= t < T_rows are zeros; every clip is analysed alone;
- *   mag_eps >= 0: mag = sqrtf((re*re + im*im) + mag_eps), squares not contracted.
+ *   mag_eps >= 0: mag = sqrtf(fma(im, im, rn(re*re)) + mag_eps): one square rounded, one fused, the sum with mag_eps rounded.
  * wav (int16 or fp32), n_samples, the packed basis [n_fft][n_fft] with its column map (the real part of bin n_fft/2 in column 32),
  * fb / fb_range, the time-major output with ldm, the clamp floor_, logf and the alignment and shape checks are those documented
  * above.  Same kernel template (csrc/melspec.hip): l2s_mel_spectrogram is this entry at (640, 160, pad 320, mag_eps 0).
@@ -698,9 +698,9 @@ int l2s_stoi_scores(const float* bands, int ldf, const int32_t* n_kept, int B, d
  *   gain: fp32 [B] = 10^(change / 20) if change = target_dbfs - 10 log10(mean(wav^2)) > 0, else 1; the squares are summed in
  *   fp64.  A clip without samples or of zeros only has no level and gets 1.
  * l2s_stft_mel_power - 40-band power mel, librosa 0.8's melspectrogram(sr 16000, n_fft 400, hop 160, n_mels 40) with center = True,
- *   csrc/spkemb.hip: the sibling of l2s_stft_mel for a frame length that is no multiple of the hop, without sqrt and log.
+ *   csrc/spkemb.hip: l2s_stft_mel's span layout (csrc/frame_dft.h) at a frame length that is no multiple of the hop, no sqrt, no log.
  *   frame t = samples [160 t - pad, 160 t - pad + 400) reflected once at either end against n_samples[b], re/im a k-ordered fp32
- *   fma chain, power = re^2 + im^2 (not contracted), band = sum over fb_range[j] in ascending bin order of fb * power.
+ *   fma chain, power = re^2 + im^2 (a square may be fused into the sum), band = sum over fb_range[j] in ascending bin order of fb * power.
  *   n_samples: int32 [B] ANALYSIS lengths (NULL = S): they set the frame count (n + 2 pad - 400) / 160 + 1 (0 unless n > pad
  *   and a frame fits) and the reflection, and may exceed S; n_valid: int32 [B] real samples (NULL = n_samples; clamped to
  *   min(n_samples, S)): positions from n_valid on are zeros and are never read - the zero padding of a clip shorter than its last

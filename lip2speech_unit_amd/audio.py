@@ -42,21 +42,29 @@ def hann_periodic(n):
     return 0.5 - 0.5 * np.cos(2.0 * np.pi * np.arange(n) / n)
 
 
+def packed_bins(c):
+    """(bin, part) of column c of a packed basis: tile q = c // 32, lane l = c % 32, bin 32 (q // 2) + l; part 0 (even tiles) is
+    w cos, part 1 (odd tiles) is -w sin - the column map of csrc/frame_dft.h."""
+    c = np.asarray(c)
+    return 32 * (c // 64) + c % 32, (c % 64) // 32
+
+
+def dft_basis(n_frame, n_dft, k, part, window):
+    """float64 [n_frame, len(k)]: column c is the window times cos (part[c] = 0) or -sin (part[c] = 1) of bin k[c] of an
+    n_dft-point DFT, over the samples of a frame; the phase is the exact integer n k reduced mod n_dft before the division."""
+    n = np.arange(n_frame)
+    ang = 2.0 * np.pi * ((n[:, None] * np.asarray(k)[None, :]) % n_dft) / n_dft
+    return np.where((np.asarray(part) == 0)[None, :], np.cos(ang), -np.sin(ang)) * np.asarray(window, dtype=np.float64)[:, None]
+
+
 def packed_basis(n_fft=640, window=None):
     """The windowed real DFT as the [n_fft, n_fft] matrix of l2s_mel_spectrogram (include/lip2speech_hip.h): row = sample,
-    column c -> tile q = c // 32, lane l = c % 32, bin k = 32 (q // 2) + l; even tiles hold w cos, odd tiles -w sin, and
-    column 32 (the imaginary part of bin 0) holds the real part of bin n_fft/2.  float64."""
+    columns by packed_bins, and column 32 (the imaginary part of bin 0) holds the real part of bin n_fft/2.  float64."""
     if n_fft % 64:
         raise ValueError("n_fft must be a multiple of 64")
-    w = hann_periodic(n_fft) if window is None else np.asarray(window, dtype=np.float64)
-    n = np.arange(n_fft)
-    c = np.arange(n_fft)
-    q, lane = c // 32, c % 32
-    k = 32 * (q // 2) + lane
-    ang = 2.0 * np.pi * ((n[:, None] * k[None, :]) % n_fft) / n_fft     # the exact integer phase, reduced before the division
-    basis = np.where((q % 2 == 0)[None, :], np.cos(ang), -np.sin(ang))
-    basis[:, 32] = np.cos(np.pi * n)
-    return basis * w[:, None]
+    k, part = packed_bins(np.arange(n_fft))
+    k[32], part[32] = n_fft // 2, 0
+    return dft_basis(n_fft, n_fft, k, part, hann_periodic(n_fft) if window is None else window)
 
 
 def unpack_spectrum(y, n_fft=640):
@@ -81,16 +89,17 @@ def band_ranges(fb):
 
 
 class _DeviceTables:
-    """basis / fb / fb_range as float32 / int32 numpy arrays on the instance, uploaded once per device."""
+    """The float32 / int32 numpy arrays named by TABLES on the instance (and a dict `_dev`), uploaded once per device."""
+    TABLES = ("basis", "fb", "fb_range")
 
     def tables(self, device):
-        """(basis, fb, fb_range) on `device`, uploaded once per device."""
+        """The TABLES arrays on `device`, in that order, uploaded once per device."""
         device = torch.device(device)
         if device.type != "cuda":
-            raise L2SError("mel analysis needs a HIP device (there is no CPU path)")
+            raise L2SError(f"{type(self).__name__} needs a HIP device (there is no CPU path)")
         key = device.index if device.index is not None else torch.cuda.current_device()
         if key not in self._dev:
-            self._dev[key] = tuple(torch.from_numpy(t).to(device) for t in (self.basis, self.fb, self.fb_range))
+            self._dev[key] = tuple(torch.from_numpy(getattr(self, t)).to(device) for t in self.TABLES)
         return self._dev[key]
 
     def _lengths(self, wav, n_samples, least):

@@ -1,27 +1,27 @@
 // The speaker encoder's ends (lip2speech_unit_amd/speaker_encoder.py; the recurrence between them is lstm.hip):
 //
 //   l2s_wav_gain        per-clip volume factor: the increase-only normalisation to -30 dBFS, mean square carried in fp64
-//   l2s_stft_mel_power  40-band POWER mel of 400-sample frames every 160 samples - melspec.hip's sibling for a frame length
-//                       that is no multiple of the hop and a linear-power epilogue (no sqrt, no log)
+//   l2s_stft_mel_power  40-band POWER mel of 400-sample frames every 160 samples - frame_dft.h's span at a frame length that is
+//                       no multiple of the hop, a K loop of its own and a linear-power epilogue (no sqrt, no log)
 //   l2s_spk_embed_head  Linear + ReLU + L2 norm per partial window, mean over a clip's windows, final L2 norm
 //
 // None of them uses an atomic; every sum runs in a fixed order, so a clip's bytes do not depend on its batch mates.
 //
 // Power mel.  A block (4 waves) owns 32 consecutive frames of one clip and stages their sample span (31 * 160 + 400 samples) in LDS
-// as hop-sized rows of stride 161 floats - melspec.hip's layout: the 32 frames of an A fragment sit 161 floats = 33 banks apart.
+// as hop-sized rows of stride 161 floats - frame_dft.h's span: the 32 frames of an A fragment sit 161 floats = 33 banks apart.
 // Reflection (against the clip's own analysis length), the zero tail past the clip's real samples, the int16 conversion and the
 // volume factor are applied while staging.  The windowed DFT is a [400, 448] fp32 table, K = 400 rows and 14 column tiles of 32:
 // tile 2 p holds w cos, tile 2 p + 1 holds -w sin of bins 32 p .. 32 p + 31; the columns of bins 201 .. 223 are zero, and adding
 // x * 0 is exact.  Wave w owns the tile pairs w and w + 4 (re and im of a bin in the same lane and register), each a k-ordered fp32
-// fma chain on v_mfma_f32_32x32x2_f32, the table read straight from L2 (it is 700 KB and shared by every block).  Powers
-// re^2 + im^2 (products and sum rounded separately, not contracted) go to LDS, and every thread folds them into 5 band sums of one
-// frame, bins ascending over fb_range.
-#include "l2s_common.h"
+// fma chain on v_mfma_f32_32x32x2_f32, the table read straight from L2 (it is 700 KB and shared by every block: with one
+// row tile per block frame_dft.h's pass loop, which stages the table in LDS, measured 1.53 ms against 1.06 ms - DESIGN.md section
+// 18).  Powers re^2 + im^2 go to LDS, and every thread folds them into 5 band sums of one frame, bins ascending over fb_range.
+#include "frame_dft.h"
 #include <math.h>
 
 namespace {
 
-typedef __attribute__((ext_vector_type(16))) float f32x16_t;
+using frame_dft::f32x16_t;
 
 // ---- fixed-order block sum of one double per thread (256 threads); the result is returned to every thread -----------------------
 __device__ __forceinline__ double block_sum_f64(double v, double* sD, int tid) {
@@ -41,13 +41,10 @@ __global__ __launch_bounds__(256) void wav_gain_kernel(const void* __restrict__ 
                                                        const int S, const double target_dbfs, float* __restrict__ gain) {
   __shared__ double sD[256];
   const int tid = threadIdx.x, b = blockIdx.x;
-  int n = n_samples ? n_samples[b] : S;
-  n = max(0, min(n, S));
+  const int n = max(0, frame_dft::clip_len(n_samples, b, S));
   double acc = 0.0;
   for (int p = tid; p < n; p += 256) {
-    float v;
-    if (I16) v = (float)((const int16_t*)wav_)[(int64_t)b * ldw + p] * (1.0f / 32768.0f);
-    else v = ((const float*)wav_)[(int64_t)b * ldw + p];
+    const float v = frame_dft::wav_sample<I16>(wav_, (int64_t)b * ldw + p);
     acc += (double)v * (double)v;
   }
   const double ss = block_sum_f64(acc, sD, tid);
@@ -62,12 +59,12 @@ __global__ __launch_bounds__(256) void wav_gain_kernel(const void* __restrict__ 
 }
 
 // ---- power mel ---------------------------------------------------------------------------------------------------------------------
-constexpr int NFFT = 400, HOP = 160, FT = 32, NMEL = 40, NBIN = NFFT / 2 + 1;
+using PowerSpan = frame_dft::FrameSpan<400, 160, 32>;
+constexpr int NFFT = PowerSpan::K, HOP = PowerSpan::HOP, FT = PowerSpan::FT, SLD = PowerSpan::SLD, NMEL = 40, NBIN = NFFT / 2 + 1;
 constexpr int NPAIR = 7, NCOL = 64 * NPAIR;              // 7 tile pairs = bins 0 .. 223
-constexpr int SPAN = (FT - 1) * HOP + NFFT, SLD = HOP + 1, SROWS = (SPAN + HOP - 1) / HOP;
 constexpr int LDG = 32 * NPAIR + 1;                      // power tile [FT][225]
 constexpr int KC = 16;                                   // k per chunk: 8 MFMA steps whose table loads are issued together
-static_assert(NFFT % KC == 0 && (SROWS * SLD + FT * LDG) * 4 <= 64 * 1024, "tile shape / static LDS");
+static_assert(NFFT % KC == 0 && (PowerSpan::SX + FT * LDG) * 4 <= 64 * 1024, "tile shape / static LDS");
 
 template <bool I16>
 __global__ __launch_bounds__(256) void mel_power_kernel(const void* __restrict__ wav_, const int64_t ldw, const int32_t* __restrict__ n_samples,
@@ -75,40 +72,21 @@ __global__ __launch_bounds__(256) void mel_power_kernel(const void* __restrict__
                                                         const float* __restrict__ basis, const float* __restrict__ fb,
                                                         const int32_t* __restrict__ fb_range, float* __restrict__ mel, const int ldm,
                                                         const int T_rows, const int pad) {
-  __shared__ float sX[SROWS * SLD];
+  __shared__ float sX[PowerSpan::SX];
   __shared__ float sG[FT * LDG];
   const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int b = blockIdx.y, f0 = blockIdx.x * FT;
   const int n = n_samples ? n_samples[b] : S;            // the analysis length: frames and reflection (may exceed the buffer)
   int nv = n_valid ? n_valid[b] : n;                     // the real samples: positions from here on are zeros and are not read
   nv = max(0, min(min(nv, n), S));
-  const int Tb = (n > pad && n + 2 * pad >= NFFT) ? (n + 2 * pad - NFFT) / HOP + 1 : 0;
+  const int Tb = frame_dft::reflect_frames<PowerSpan>(n, pad);
   const int rows = min(FT, T_rows - f0);
   float* __restrict__ out = mel + ((int64_t)b * T_rows + f0) * ldm;
   if (f0 >= Tb) {                                        // block-uniform: a tile wholly past the clip's end
-    for (int e = tid; e < rows * NMEL; e += 256) {
-      const int r = e / NMEL;
-      out[(int64_t)r * ldm + (e - r * NMEL)] = 0.f;
-    }
+    frame_dft::zero_tile(out, rows, NMEL, ldm);
     return;
   }
-  {
-    const float g = scale ? scale[b] : 1.0f;
-    const int p0 = f0 * HOP - pad;
-    for (int s = tid; s < SROWS * HOP; s += 256) {
-      int p = p0 + s;
-      p = p < 0 ? -p : p;
-      p = p >= n ? 2 * (n - 1) - p : p;
-      float v = 0.f;
-      if (s < SPAN && (unsigned)p < (unsigned)nv) {
-        if (I16) v = (float)((const int16_t*)wav_)[(int64_t)b * ldw + p] * (1.0f / 32768.0f);
-        else v = ((const float*)wav_)[(int64_t)b * ldw + p];
-        if (scale) v = __fmul_rn(v, g);
-      }
-      const int r = s / HOP;
-      sX[r * SLD + (s - r * HOP)] = v;
-    }
-  }
+  frame_dft::stage_span<PowerSpan, I16>(sX, wav_, ldw, b, f0 * HOP - pad, n, nv, scale);
   __syncthreads();
 
   const int lr = lane & 31, lh = lane >> 5;

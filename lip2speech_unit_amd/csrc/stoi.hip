@@ -10,12 +10,10 @@
 // Nothing here uses an atomic: every sum has one fixed order, so a clip's results are the same bytes from run to run and whatever
 // its batch mates are.  Samples, spectra and normalisations are fp32; sums of squares that decide the mask and the sums over
 // bands, frames and segments are carried in fp64.
-#include "l2s_common.h"
+#include "frame_dft.h"
 #include <math.h>
 
 namespace {
-
-typedef __attribute__((ext_vector_type(16))) float f32x16_t;
 
 constexpr int FRAME = 256, HOP = 128, NBAND = 15, NSEG = 30;
 constexpr int BIN0 = 7, BIN1 = 219;                      // the bins the 15 bands cover: [7, 219)
@@ -30,11 +28,7 @@ __host__ __device__ __forceinline__ int frames_of(int len) { return len > FRAME 
 static_assert(MAX_LEN10K % 5 == 0 && (5 * MAX_SAMPLES + 7) / 8 == MAX_LEN10K && (5 * (MAX_SAMPLES + 1) + 7) / 8 > MAX_LEN10K, "cap");
 inline bool size_ok(int S) { return S > 0 && S <= MAX_SAMPLES; }
 
-__device__ __forceinline__ int clip_samples(const int32_t* n_samples, int b, int S) {
-  int n = n_samples ? n_samples[b] : S;
-  n = n < S ? n : S;
-  return n > 0 ? n : 0;
-}
+__device__ __forceinline__ int clip_samples(const int32_t* n_samples, int b, int S) { return max(frame_dft::clip_len(n_samples, b, S), 0); }
 
 __device__ __forceinline__ double wave_sum_f64(double v) {
 #pragma unroll
@@ -68,10 +62,7 @@ __global__ __launch_bounds__(RS_OUT) void stoi_resample_kernel(const void* __res
   for (int s = tid; s < RS_SPAN; s += RS_OUT) {
     const int p = lo + s;
     float v = 0.f;
-    if ((unsigned)p < (unsigned)n) {
-      if (I16) v = (float)((const int16_t*)wav_)[(int64_t)b * ldw + p] * (1.0f / 32768.0f);
-      else v = ((const float*)wav_)[(int64_t)b * ldw + p];
-    }
+    if ((unsigned)p < (unsigned)n) v = frame_dft::wav_sample<I16>(wav_, (int64_t)b * ldw + p);
     sX[s] = v;
   }
   for (int s = tid; s < RS_PH * RS_Q; s += RS_OUT) sT[s] = taps[s];
@@ -157,15 +148,12 @@ __global__ __launch_bounds__(FR_WAVES * 64) void stoi_frames_kernel(const float*
 // The compacted signal z (kept windowed frames overlap-added at hop 128) is chunk c = samples [128 c, 128 c + 128):
 //   z[128 c + r] = W[128 + r] x[128 g(c-1) + 128 + r] + W[r] x[128 g(c) + r],   g(k) = the k-th kept frame, terms outside 0 <= k < K drop.
 // Frame f of the second analysis is chunks f, f + 1; there are F = K - 1 of them.  A block owns 32 consecutive frames of one signal
-// of one clip: it gathers their 33 chunks into LDS (rows of 128 with stride 129, so the 32 frames of an MFMA A fragment sit on 32
-// distinct banks) and multiplies [32 x 256] by the basis [256 x 512] - the second window folded in, column map in the header - in
-// two passes of 256 columns, K-tiles of 8 rows streamed global -> registers -> LDS double buffered, exactly the loop of melspec.hip:
-// wave pp owns the re and im tiles of bins 7 + 128 pass + 32 pp .. + 31, in the same lane and register.  After a pass the 32 x 128
-// powers go to LDS over the basis buffers and thread (frame tid % 32, band group tid / 32) adds its bands' bins in ascending order.
-constexpr int BT_F = 32, BT_CH = BT_F + 1, BT_LDZ = HOP + 1;
-constexpr int BT_K = FRAME, BT_NCOL = 512, BT_PN = 256, BT_LDB = BT_PN + 4, BT_BK = 8, BT_KT = BT_K / BT_BK, BT_NPASS = BT_NCOL / BT_PN;
-constexpr int BT_NBP = BT_PN / 2, BT_LDP = BT_NBP + 1;
-static_assert(BT_F * BT_LDP <= 2 * BT_BK * BT_LDB, "the power tile reuses the basis buffers");
+// of one clip: it gathers their 33 chunks into the span rows of frame_dft.h (rows of 128 with stride 129) and that header's pass
+// loop multiplies [32 x 256] by the basis [256 x 512] - the second window folded in, column map in the ABI header - in two passes
+// of 256 columns: wave pp owns the re and im tiles of bins 7 + 128 pass + 32 pp .. + 31.  After a pass the 32 x 128 powers are in
+// the result tile and thread (frame tid % 32, band group tid / 32) adds its bands' bins in ascending order.
+using BandTile = frame_dft::FrameDftTile<FRAME, HOP, 32, 512>;
+constexpr int BT_F = BandTile::FT, BT_CH = BandTile::SROWS;
 
 __global__ __launch_bounds__(256, 2) void stoi_bands_kernel(const float* __restrict__ x, const float* __restrict__ y, const int64_t ldx,
                                                             const int32_t* __restrict__ n_samples, const int S,
@@ -173,10 +161,11 @@ __global__ __launch_bounds__(256, 2) void stoi_bands_kernel(const float* __restr
                                                             const int32_t* __restrict__ n_kept, const float* __restrict__ window,
                                                             const float* __restrict__ basis, const int32_t* __restrict__ band_edges,
                                                             float* __restrict__ bands, const int ldf) {
-  __shared__ float sZ[BT_CH * BT_LDZ];
-  __shared__ __attribute__((aligned(16))) float sB[2 * BT_BK * BT_LDB];
+  constexpr int LDZ = BandTile::SLD, NBP = BandTile::NBP, LDP = BandTile::LDR;
+  __shared__ float sZ[BandTile::SX];
+  __shared__ __attribute__((aligned(16))) float sB[BandTile::SB];
   __shared__ int sG[BT_CH + 1];
-  const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int tid = threadIdx.x;
   const int f0 = blockIdx.x * BT_F, sig = blockIdx.y, b = blockIdx.z;
   const int nf = min(frames_of(len10k(clip_samples(n_samples, b, S))), MAX_FRAMES);
   const int K = max(min(min(n_kept[b], nf), ldk), 0);
@@ -184,10 +173,7 @@ __global__ __launch_bounds__(256, 2) void stoi_bands_kernel(const float* __restr
   const int rows = min(BT_F, ldf - f0);                  // columns of this tile that exist in the output (>= 1 by the grid)
   float* __restrict__ out = bands + ((int64_t)(b * 2 + sig) * NBAND) * ldf + f0;
   if (f0 >= F) {                                         // block-uniform: a tile wholly past the clip's frames
-    for (int e = tid; e < NBAND * rows; e += 256) {
-      const int j = e / rows;
-      out[(int64_t)j * ldf + (e - j * rows)] = 0.f;
-    }
+    frame_dft::zero_tile(out, NBAND, rows, ldf);
     return;
   }
 
@@ -205,26 +191,10 @@ __global__ __launch_bounds__(256, 2) void stoi_bands_kernel(const float* __restr
       const int g0 = sG[ci], g1 = sG[ci + 1];
       float v = g0 >= 0 ? __fmul_rn(window[HOP + r], src[(int64_t)g0 * HOP + HOP + r]) : 0.f;
       if (g1 >= 0) v = fmaf(window[r], src[(int64_t)g1 * HOP + r], v);
-      sZ[ci * BT_LDZ + r] = v;
+      sZ[ci * LDZ + r] = v;
     }
   }
 
-  // ---- basis fetch: thread -> rows tid / 64 and that + 4 of the K-tile, columns 4 (tid % 64) .. + 3
-  const int ld_k = tid / (BT_PN / 4), ld_c = (tid % (BT_PN / 4)) * 4;
-  float4 rb0, rb1;
-  auto fetch = [&](int t) {                              // t: flat K-tile index, pass = t / BT_KT
-    const int pass = t / BT_KT, k0 = (t - pass * BT_KT) * BT_BK;
-    const float* src = basis + (int64_t)(k0 + ld_k) * BT_NCOL + pass * BT_PN + ld_c;
-    rb0 = *reinterpret_cast<const float4*>(src);
-    rb1 = *reinterpret_cast<const float4*>(src + (BT_BK / 2) * BT_NCOL);
-  };
-  auto stage = [&](int buf) {
-    *reinterpret_cast<float4*>(&sB[(buf * BT_BK + ld_k) * BT_LDB + ld_c]) = rb0;
-    *reinterpret_cast<float4*>(&sB[(buf * BT_BK + ld_k + BT_BK / 2) * BT_LDB + ld_c]) = rb1;
-  };
-
-  const int pp = wave, lr = lane & 31, lh = lane >> 5;
-  const int arow = lr * BT_LDZ;
   const int mf = tid % BT_F, mg = tid / BT_F;            // the frame and the band group (bands mg, mg + 8) of this thread's sums
   int e_lo[2], e_hi[2];
 #pragma unroll
@@ -234,57 +204,17 @@ __global__ __launch_bounds__(256, 2) void stoi_bands_kernel(const float* __restr
     e_hi[j] = band < NBAND ? min(band_edges[band + 1], BIN1) : BIN1;
   }
   float m[2] = {0.f, 0.f};
-  f32x16_t acc[2];
+  frame_dft::pass_loop<BandTile>(
+      sZ, sB, basis,
+      [](int, int, float re, float im) { return frame_dft::power(im, re); },   // powers of bins 7 + 128 pass ..: fma(re, re, rn(im im))
+      [&](int pass, const float* sP) {                   // ... into the band sums, bins ascending
+        const int c0 = BIN0 + pass * NBP;
 #pragma unroll
-  for (int e = 0; e < 16; ++e) { acc[0][e] = 0.f; acc[1][e] = 0.f; }
-
-  constexpr int NT = BT_NPASS * BT_KT;
-  fetch(0);
-  stage(0);
-  __syncthreads();
-  for (int t = 0; t < NT; ++t) {
-    const int buf = t & 1;
-    const int pass = t / BT_KT, kt = t - pass * BT_KT;
-    if (t + 1 < NT) fetch(t + 1);
-    const float* bt = &sB[buf * BT_BK * BT_LDB + 64 * pp + lr];
-#pragma unroll
-    for (int s = 0; s < BT_BK / 2; ++s) {
-      const int k = kt * BT_BK + 2 * s + lh;
-      const int q = k / HOP;
-      const float a = sZ[arow + q * BT_LDZ + (k - q * HOP)];
-      const float w0 = bt[(2 * s + lh) * BT_LDB], w1 = bt[(2 * s + lh) * BT_LDB + 32];
-      acc[0] = __builtin_amdgcn_mfma_f32_32x32x2f32(a, w0, acc[0], 0, 0, 0);
-      acc[1] = __builtin_amdgcn_mfma_f32_32x32x2f32(a, w1, acc[1], 0, 0, 0);
-    }
-    if (kt + 1 < BT_KT) {
-      stage(buf ^ 1);
-      __syncthreads();
-      continue;
-    }
-    // ---- end of a pass: powers of bins 7 + 128 pass .. + 127 -> LDS -> the band sums
-    __syncthreads();                                     // every wave is done with the basis buffers
-    float* sP = sB;
-#pragma unroll
-    for (int e = 0; e < 16; ++e) {
-      const int fr = 8 * (e >> 2) + 4 * lh + (e & 3);
-      const float re = acc[0][e], im = acc[1][e];
-      sP[fr * BT_LDP + 32 * pp + lr] = __fadd_rn(__fmul_rn(re, re), __fmul_rn(im, im));
-      acc[0][e] = 0.f;
-      acc[1][e] = 0.f;
-    }
-    __syncthreads();
-    const int c0 = BIN0 + pass * BT_NBP;
-#pragma unroll
-    for (int j = 0; j < 2; ++j) {
-      const int lo = max(e_lo[j], c0), hi = min(e_hi[j], c0 + BT_NBP);
-      for (int k = lo; k < hi; ++k) m[j] += sP[mf * BT_LDP + (k - c0)];
-    }
-    __syncthreads();                                     // the power tile is read: the buffers go back to the basis
-    if (t + 1 < NT) {
-      stage(buf ^ 1);
-      __syncthreads();
-    }
-  }
+        for (int j = 0; j < 2; ++j) {
+          const int lo = max(e_lo[j], c0), hi = min(e_hi[j], c0 + NBP);
+          for (int k = lo; k < hi; ++k) m[j] += sP[mf * LDP + (k - c0)];
+        }
+      });
 
   if (mf < rows) {
 #pragma unroll

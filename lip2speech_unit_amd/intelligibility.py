@@ -14,7 +14,7 @@ correlation measures over every 30-frame segment.  The tables are numpy float64 
 import numpy as np
 import torch
 
-from . import ops
+from . import audio, ops
 from ._lib import L2SError
 
 FS = 10000
@@ -58,23 +58,22 @@ def band_edges():
 
 def basis_bin(c):
     """(bin, part) of column c of the packed basis: part 0 = cos, 1 = -sin (the column map of l2s_stoi_bands)."""
-    c = np.asarray(c)
-    return BIN0 + 128 * (c // 256) + 32 * ((c % 256) // 64) + c % 32, (c % 64) // 32
+    k, part = audio.packed_bins(c)
+    return BIN0 + k, part
 
 
 def packed_basis():
     """float64 [256, 512]: row n = sample of a frame with the analysis window folded in, columns by basis_bin; bins the bands do
     not read (219 and above) are zeros."""
-    n = np.arange(N_FRAME)
     k, part = basis_bin(np.arange(2 * N_FRAME))
-    ang = 2.0 * np.pi * ((n[:, None] * k[None, :]) % NFFT) / NFFT          # the exact integer phase, reduced before the division
-    b = np.where((part == 0)[None, :], np.cos(ang), -np.sin(ang)) * window()[:, None]
+    b = audio.dft_basis(N_FRAME, NFFT, k, part, window())
     b[:, k >= band_edges()[-1]] = 0.0
     return b
 
 
-class STOI:
+class STOI(audio._DeviceTables):
     """Scores batches of clip pairs on the device; the tables are built once and uploaded once per device."""
+    TABLES = ("taps", "window", "basis", "band_edges")
 
     def __init__(self, sampling_rate=16000):
         if sampling_rate != 16000:
@@ -85,16 +84,6 @@ class STOI:
         self.basis = packed_basis().astype(np.float32)
         self.band_edges = band_edges()
         self._dev = {}
-
-    def tables(self, device):
-        """(taps, window, basis, band_edges) on `device`, uploaded once per device."""
-        device = torch.device(device)
-        if device.type != "cuda":
-            raise L2SError("STOI needs a HIP device (there is no CPU path)")
-        key = device.index if device.index is not None else torch.cuda.current_device()
-        if key not in self._dev:
-            self._dev[key] = tuple(torch.from_numpy(t).to(device) for t in (self.taps, self.window, self.basis, self.band_edges))
-        return self._dev[key]
 
     def stages(self, clean, processed, n_samples=None):
         """Everything the four entries produce for device tensors clean / processed [B, S] (fp32 in (-1, 1) or int16 PCM, one dtype)

@@ -47,18 +47,11 @@ def compute_partial_slices(n_samples, rate=1.3, min_coverage=0.75):
 
 
 def power_basis(n_fft=MEL_N_FFT, cols=BASIS_COLS):
-    """The windowed real DFT as the [n_fft, cols] table of l2s_stft_mel_power (include/lip2speech_hip.h): column c -> tile
-    q = c // 32, lane l = c % 32, bin k = 32 (q // 2) + l; even tiles w cos, odd tiles -w sin; zero columns past bin n_fft/2 and
-    for the imaginary parts of bins 0 and n_fft/2.  float64."""
-    w = audio.hann_periodic(n_fft)
-    n = np.arange(n_fft)
-    c = np.arange(cols)
-    q, lane = c // 32, c % 32
-    k = 32 * (q // 2) + lane
-    ang = 2.0 * np.pi * ((n[:, None] * k[None, :]) % n_fft) / n_fft
-    basis = np.where((q % 2 == 0)[None, :], np.cos(ang), -np.sin(ang)) * w[:, None]
-    basis[:, k > n_fft // 2] = 0.0
-    basis[:, (q % 2 == 1) & ((k == 0) | (k == n_fft // 2))] = 0.0
+    """The windowed real DFT as the [n_fft, cols] table of l2s_stft_mel_power (include/lip2speech_hip.h): columns by
+    audio.packed_bins; zero columns past bin n_fft/2 and for the imaginary parts of bins 0 and n_fft/2.  float64."""
+    k, part = audio.packed_bins(np.arange(cols))
+    basis = audio.dft_basis(n_fft, n_fft, k, part, audio.hann_periodic(n_fft))
+    basis[:, (k > n_fft // 2) | ((part == 1) & ((k == 0) | (k == n_fft // 2)))] = 0.0
     return basis
 
 
