@@ -16,6 +16,7 @@ import torch.nn as nn
 
 from . import ops
 from .ops import ACT_GELU, ACT_RELU, F_MASK, F_RES_POST, MODE_CONV1D
+from .packing import PackedState
 
 
 @dataclass
@@ -121,7 +122,7 @@ class RavenEncoderLayer(nn.Module):
         self.gamma_mha = nn.Parameter(0.1 * torch.ones(d))
 
 
-class Encoder(nn.Module):
+class Encoder(nn.Module, PackedState):
     """ESPnet Encoder (encoder.py:55-306) with input_layer 'conv3d' (embed.0 Linear(512,d) + rel-pos), macaron conformer
     blocks (rel_mha, cnn module k=31), after_norm.  `frontend` is None for the conformer head (model_avhubert.py:206) and a
     Conv3dResNet for the `multi_target` / Auto-AVSR encoders."""
@@ -135,10 +136,12 @@ class Encoder(nn.Module):
                                        for _ in range(blocks)])
         self.after_norm = nn.LayerNorm(d, eps=1e-12)
         self.d, self.heads, self.hidden, self.k = d, heads, hidden, k
-        self._packed = None
-        self._pos_cache = {}
+        self._init_packed()
         if d // heads != 64:
             raise NotImplementedError("the attention kernels are built for 64-dim heads (512/8, 768/12, 1024/16)")
+
+    def _covers(self, dtype):
+        return self._packed["dtype"] == dtype
 
     def pack(self, dev, dtype):
         t16 = ops.torch_dtype(dtype)
@@ -204,18 +207,16 @@ class Encoder(nn.Module):
             P["layers"].append(e)
         P["w_pos"] = w16(torch.cat(pos_w, 0))                                           # [layers*d, d]
         P["n_after"] = _ln(self.after_norm, dev)
-        self._packed = P
-        self._pos_cache = {}
-        return P
+        return self._set_packed(dev, P)
 
     def _pos_proj(self, T, dev):
-        """linear_pos(pos_emb) for all layers at once (attention.py:257): [2T-1, layers*d] 16-bit, cached per T.  Building it
-        copies a host table, which a hipGraph capture of a new bucket length could not do - and a captured graph keeps the
-        raw device pointer of its entry, so entries are NEVER evicted (each is (2T-1) * layers * d * 2 bytes: 4.9 MB at
-        T = 200, 29 MB at the service's 24-s limit); the cache is dropped only with the weights (pack / load_state_dict),
-        which invalidates captured graphs anyway."""
-        key = (T, str(dev))
-        if key not in self._pos_cache:
+        """linear_pos(pos_emb) for all layers at once (attention.py:257): [2T-1, layers*d] 16-bit, derived state cached per T.
+        Building it copies a host table, which a hipGraph capture of a new bucket length could not do - and a captured graph
+        keeps the raw device pointer of its entry, so entries are NEVER evicted (each is (2T-1) * layers * d * 2 bytes: 4.9 MB
+        at T = 200, 29 MB at the service's 24-s limit); they are dropped only with the weights (a repack, a load_state_dict,
+        invalidate()), each of which moves packing.state_epoch - the value a pipeline.GraphCache built with `state=` watches
+        to drop its captures."""
+        def build():
             P, d = self._packed, self.d
             dt = P["dtype"]
             t16 = ops.torch_dtype(dt)
@@ -223,16 +224,14 @@ class Encoder(nn.Module):
             nl = len(P["layers"])
             out = torch.empty(2 * T - 1, nl * d, device=dev, dtype=t16)
             ops.tapgemm(pe, P["w_pos"], out, M=2 * T - 1, N=nl * d, Cin=d, dtype=dt)
-            self._pos_cache[key] = out
-        return self._pos_cache[key]
+            return out
+        return self.derived((T, str(dev)), build)
 
     def forward_rows(self, xin, lens, B, T, len_mul, dtype):
         """forward_after_frontend (encoder.py:285-306) up to, not including, after_norm: xin [B*T, idim] 16-bit rows (b,t) ->
         the fp32 residual stream [B*T, d] after the last block.  lens: int32 [B], valid rows = lens*len_mul."""
         dev = xin.device
-        if self._packed is None or self._packed["b_emb"].device != dev or self._packed["dtype"] != dtype:
-            self.pack(dev, dtype)
-        P, dt = self._packed, dtype
+        P, dt = self.packed(dev, dtype=dtype), dtype
         t16 = ops.torch_dtype(dt)
         d, H, F, k = self.d, self.heads, self.hidden, self.k
         M = B * T
@@ -300,7 +299,7 @@ def rel_pos_table(T, d, dev):
     return pe.to(dev)
 
 
-class Conformer(nn.Module):
+class Conformer(nn.Module, PackedState):
     """model_avhubert.py:182-319."""
 
     def __init__(self, cfg: ConformerConfig = None, dtype=ops.F16):
@@ -319,21 +318,7 @@ class Conformer(nn.Module):
         self.mel_proj = nn.Linear(d, cfg.mel_dim)
         self.text_classifier = TextClassifier(d, cfg.text_classes) if cfg.text_supervision else None
         self.dtype = dtype
-        self._packed = None
-
-    @property
-    def _pos_cache(self):
-        return self.encoder._pos_cache
-
-    @_pos_cache.setter
-    def _pos_cache(self, v):
-        self.encoder._pos_cache = v
-
-    def load_state_dict(self, *a, **k):
-        r = super().load_state_dict(*a, **k)
-        self._packed = None
-        self.encoder._packed, self.encoder._pos_cache = None, {}
-        return r
+        self._init_packed()
 
     def pack(self, dev):
         t16 = ops.torch_dtype(self.dtype)
@@ -370,16 +355,13 @@ class Conformer(nn.Module):
             b = torch.full((Vp,), -torch.finfo(torch.float32).max)
             b[:V] = lin.bias.detach().float().cpu()
             P["w_text"], P["b_text"], P["v_text"] = w16(w), b.to(dev).contiguous(), V
-        P["dev_probe"] = P["b_mel"]
-        self._packed = P
+        self._set_packed(dev, P)
 
     def forward_rows(self, src16, lens, B, T, spk_emb, len_mul=2):
         """src16: [B*T, 1024] 16-bit rows (b,t) at the 50 Hz rate; lens: int32 [B] in video frames (len_mul=2).
         Returns (logits fp32 [B*T, V], mel fp32 [B*T, 160] == [B, 2T, 80], y16 [B*T, d])."""
         dev = src16.device
-        if self._packed is None or self._packed["dev_probe"].device != dev:
-            self.pack(dev)
-        P, dt, cfg = self._packed, self.dtype, self.cfg
+        P, dt, cfg = self.packed(dev), self.dtype, self.cfg
         t16 = ops.torch_dtype(dt)
         d = cfg.conformer_embed_dim
         M = B * T
@@ -389,11 +371,13 @@ class Conformer(nn.Module):
         else:
             xin = src16
         x = self.encoder.forward_rows(xin, lens, B, T, len_mul, dt)                      # :259-265 forward_after_frontend
-        # after_norm (encoder.py:303-304): y16 feeds proj_out; a masked copy lands in the mel-head concat buffer
+        # after_norm (encoder.py:303-304): y16 feeds proj_out; a masked copy lands in the mel-head concat buffer.  Read from
+        # the encoder's own state (P["n_after"] is that pair as of pack()): the encoder alone may have reloaded since
+        na = self.encoder._packed["n_after"]
         y16 = torch.empty(M, d, device=dev, dtype=t16)
         cat = torch.empty(M, d + cfg.spk_dim, device=dev, dtype=t16)
-        ops.layernorm(x, P["n_after"][0], P["n_after"][1], 1e-12, y16, M=M, C=d, dtype=dt)
-        ops.layernorm(x, P["n_after"][0], P["n_after"][1], 1e-12, cat[:, cfg.spk_dim:], M=M, C=d, ldy=d + cfg.spk_dim,
+        ops.layernorm(x, na[0], na[1], 1e-12, y16, M=M, C=d, dtype=dt)
+        ops.layernorm(x, na[0], na[1], 1e-12, cat[:, cfg.spk_dim:], M=M, C=d, ldy=d + cfg.spk_dim,
                       lens=lens, len_mul=len_mul, mask_T=T, dtype=dt)
         assert spk_emb.size(-1) == cfg.spk_dim                                           # model_avhubert.py:268
         spk = spk_emb.contiguous()
@@ -427,9 +411,7 @@ class Conformer(nn.Module):
         if self.text_classifier is None:
             raise RuntimeError("this conformer has no text head (TEXT_SUPERVISION=0)")
         dev = y16.device
-        if self._packed is None or self._packed["dev_probe"].device != dev:
-            self.pack(dev)
-        P, d = self._packed, self.cfg.conformer_embed_dim
+        P, d = self.packed(dev), self.cfg.conformer_embed_dim
         M, Vp = y16.shape[0], P["w_text"].shape[0]
         out = torch.empty(M, Vp, device=dev, dtype=torch.float32)
         ops.tapgemm(y16, P["w_text"], out, M=M, N=Vp, Cin=d, bias=P["b_text"], dtype=self.dtype)

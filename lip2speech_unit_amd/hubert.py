@@ -13,6 +13,7 @@ import torch.nn as nn
 
 from . import ops
 from .ops import ACT_GELU, F_DUAL, F_MASK, F_RES_POST, MODE_CONV1D
+from .packing import PackedState
 from .resnet import ResEncoder
 
 
@@ -91,7 +92,7 @@ class _WeightNormConv1d(nn.Module):
         self.bias = nn.Parameter(torch.zeros(cout))
 
 
-class TransformerEncoder(nn.Module):
+class TransformerEncoder(nn.Module, PackedState):
     """fairseq TransformerEncoder (called at hubert.py:739): pos_conv + N pre-LN layers + final layer_norm, or with
     layer_norm_first=False (HuBERT-base, speech_units.py) pos_conv + layer_norm + N post-LN layers."""
 
@@ -105,7 +106,10 @@ class TransformerEncoder(nn.Module):
              for _ in range(cfg.encoder_layers)])
         self.layer_norm = nn.LayerNorm(d, eps=1e-5)
         self.dtype = dtype
-        self._packed = None
+        self._init_packed()
+
+    def _covers(self, n_layers=None):
+        return len(self._packed["layers"]) >= (len(self.layers) if n_layers is None else n_layers)
 
     def pack(self, dev, n_layers=None):
         """Upload the packed weights; n_layers: only the first n_layers layers (an early exit never needs the rest)."""
@@ -142,7 +146,7 @@ class TransformerEncoder(nn.Module):
             P["layers"].append(e)
         P["lnf"] = (self.layer_norm.weight.detach().float().to(dev).contiguous(),
                     self.layer_norm.bias.detach().float().to(dev).contiguous())
-        self._packed = P
+        self._set_packed(dev, P)
 
     def forward_rows(self, x32, x16, lens, B, T, output_layer=None):
         """x32/x16: [B*T, d] fp32 / 16-bit copies of the input with padded rows already zeroed.  Returns fp32 [B*T, d].
@@ -152,9 +156,7 @@ class TransformerEncoder(nn.Module):
         if output_layer is not None:
             raise NotImplementedError("output_layer is built for layer_norm_first=False only")
         dev = x32.device
-        if self._packed is None or self._packed["pc_b"].device != dev:
-            self.pack(dev)
-        P, dt, cfg = self._packed, self.dtype, self.cfg
+        P, dt, cfg = self.packed(dev), self.dtype, self.cfg
         t16 = ops.torch_dtype(dt)
         d, H, F = cfg.encoder_embed_dim, cfg.encoder_attention_heads, cfg.encoder_ffn_embed_dim
         G, k = cfg.conv_pos_groups, cfg.conv_pos
@@ -199,11 +201,7 @@ class TransformerEncoder(nn.Module):
         n = len(self.layers) if output_layer is None else int(output_layer)
         if not 0 <= n <= len(self.layers):
             raise ValueError(f"output_layer={output_layer}: the encoder has {len(self.layers)} layers")
-        P = self._packed
-        if P is None or P["pc_b"].device != dev or len(P["layers"]) < n:
-            self.pack(dev, n)
-            P = self._packed
-        dt, cfg = self.dtype, self.cfg
+        P, dt, cfg = self.packed(dev, n_layers=n), self.dtype, self.cfg
         t16 = ops.torch_dtype(dt)
         d, H, F = cfg.encoder_embed_dim, cfg.encoder_attention_heads, cfg.encoder_ffn_embed_dim
         G, k = cfg.conv_pos_groups, cfg.conv_pos
@@ -246,7 +244,7 @@ class SubModel(nn.Module):
         self.encoder = None
 
 
-class AVHubertModel(nn.Module):
+class AVHubertModel(nn.Module, PackedState):
     """Inference subset of avhubert/hubert.py:334-440: video-only extract_finetune."""
 
     def __init__(self, cfg: AVHubertConfig = None, dtype=ops.F16):
@@ -266,31 +264,21 @@ class AVHubertModel(nn.Module):
         self.encoder = TransformerEncoder(cfg, dtype=dtype)
         self.layer_norm = nn.LayerNorm(self.embed, eps=1e-5)
         self.dtype = dtype
-        self._packed = None
+        self._init_packed()
 
     def pack(self, dev):
         t16 = ops.torch_dtype(self.dtype)
         fv = self.feature_extractor_video
-        self._packed = {
+        self._set_packed(dev, {
             "wp": fv.proj.weight.detach().to(dev, t16).contiguous(),
             "bp": fv.proj.bias.detach().float().to(dev).contiguous(),
             "ln": (self.layer_norm.weight.detach().float().to(dev).contiguous(),
                    self.layer_norm.bias.detach().float().to(dev).contiguous()),
             "wpe": self.post_extract_proj.weight.detach().to(dev, t16).contiguous(),
             "bpe": self.post_extract_proj.bias.detach().float().to(dev).contiguous(),
-        }
+        })
         fv.resnet.pack(dev)
         self.encoder.pack(dev)
-
-    def repack(self):
-        self._packed = None
-        self.encoder._packed = None
-        self.feature_extractor_video.resnet._packed = None
-
-    def load_state_dict(self, *a, **k):
-        r = super().load_state_dict(*a, **k)
-        self.repack()
-        return r
 
     @staticmethod
     def lens_from_padding_mask(padding_mask, B, T, dev):
@@ -305,9 +293,7 @@ class AVHubertModel(nn.Module):
     def extract_rows(self, video, padding_mask):
         """Hot path: video [B,1,T,88,88], padding_mask [B,T] bool or None -> (fp32 [B*T, d] rows (b,t), lens int32 [B])."""
         dev = video.device
-        if self._packed is None or self._packed["bp"].device != dev:
-            self.pack(dev)
-        P, dt = self._packed, self.dtype
+        P, dt = self.packed(dev), self.dtype
         t16 = ops.torch_dtype(dt)
         d = self.encoder_embed_dim
         feat, B, T = self.feature_extractor_video.resnet.forward_rows(video)         # hubert.py:707 -> :324-326

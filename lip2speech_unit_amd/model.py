@@ -141,11 +141,6 @@ class Conformer(_ConformerHead):
         super().__init__(cfg, dtype=dtype)
         self.encoder.frontend = Conv3dResNet(relu_type="swish", dtype=dtype)
 
-    def load_state_dict(self, *a, **k):
-        r = super().load_state_dict(*a, **k)
-        self.encoder.frontend._packed = None
-        return r
-
     def frontend_weight_checksum(self):
         s = 0.0
         for name, p in self.encoder.frontend.named_parameters():

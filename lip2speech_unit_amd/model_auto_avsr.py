@@ -47,12 +47,6 @@ class AutoAVSREncoder(nn.Module):
         self.encoder.frontend = Conv3dResNet(relu_type="swish", dtype=dtype)
         self.dtype = dtype
 
-    def load_state_dict(self, *a, **k):
-        r = super().load_state_dict(*a, **k)
-        self.encoder._packed, self.encoder._pos_cache = None, {}
-        self.encoder.frontend._packed = None
-        return r
-
     def extract_rows(self, video, padding_mask):
         """Encoder.forward (espnet encoder.py:230-259): video [B,1,T,88,88] -> (fp32 [B*T, d] rows (b,t), lens int32 [B], B, T)."""
         enc, dt = self.encoder, self.dtype
@@ -99,11 +93,8 @@ class MultiTargetAutoAVSREncoderModel(ModelBase):
         return cls(AutoAVSREncoder(encoder_cfg, dtype=dtype), tgt_dict, cfg, conformer)
 
     def load_state_dict(self, state_dict, strict=True, model_cfg=None, args=None):
-        r = nn.Module.load_state_dict(self, state_dict, strict=strict)
-        self.encoder.encoder._packed, self.encoder.encoder._pos_cache = None, {}
-        self.encoder.encoder.frontend._packed = None
-        self.conformer._packed = None
-        return r
+        # (BaseFairseqModel.load_state_dict's signature)
+        return nn.Module.load_state_dict(self, state_dict, strict=strict)
 
     def forward(self, **kwargs):
         out = self.encoder(source=kwargs["source"], padding_mask=kwargs["padding_mask"])

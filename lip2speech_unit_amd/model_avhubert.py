@@ -75,10 +75,7 @@ class MultiTargetAVHubertEncoderModel(ModelBase):
 
     def load_state_dict(self, state_dict, strict=True, model_cfg=None, args=None):
         # (BaseFairseqModel.load_state_dict's signature; its upgrade / prune hooks have nothing to do for this model)
-        r = nn.Module.load_state_dict(self, state_dict, strict=strict)
-        self.encoder.w2v_model.repack()
-        self.conformer._packed, self.conformer._pos_cache = None, {}
-        return r
+        return nn.Module.load_state_dict(self, state_dict, strict=strict)
 
     def load_checkpoint_state(self, state_dict, check_resnet_sum=True, expected_resnet_sum=RESNET_WEIGHT_SUM):
         """Load a released checkpoint's `state["model"]` (multi_target_lip2speech/inference.py:116 ->

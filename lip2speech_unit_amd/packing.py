@@ -1,7 +1,67 @@
-"""Host-side weight packing for the tap-GEMM layouts (pure tensor re-layout, done once at load time)."""
+"""Host-side weight packing for the tap-GEMM layouts (pure tensor re-layout, done once at load time), and the protocol by
+which a module owns its packed copy (`PackedState`)."""
+import itertools
 from typing import Dict, List
 
 import torch
+
+_clock = itertools.count(1)   # process-wide: a stamp is never handed out twice
+
+
+def _device(dev):
+    """torch.device with the index filled in: pack("cuda") and a forward on cuda:0 are the same place."""
+    dev = torch.device(dev)
+    if dev.type == "cuda" and dev.index is None:
+        dev = torch.device("cuda", torch.cuda.current_device())
+    return dev
+
+
+def _invalidate_on_load(module, incompatible_keys):
+    """load_state_dict post-hook.  torch runs the post-hooks of every submodule of the module that loads, so each PackedState
+    drops its own state whichever ancestor (or the module itself) was loaded into.  A module-level function, so that models
+    still deep-copy and pickle, and a copy's hook reaches the copy."""
+    module.invalidate()
+
+
+class PackedState:
+    """Mixin for an nn.Module that keeps its weights in kernel layout on the device.  The class's `pack(dev, ...)` builds the
+    dict and hands it to `_set_packed`; forwards fetch it with `packed(dev, ...)`.  `_packed` lives until the module (or an
+    ancestor) loads a state dict or `invalidate()` is called - which code that edits parameters in place has to do itself.
+    `derived(key, build)` holds whatever else is built on demand from the weights and must die with them."""
+
+    def _init_packed(self):
+        self._packed, self._packed_dev, self._derived = None, None, {}
+        self._epoch = next(_clock)
+        self.register_load_state_dict_post_hook(_invalidate_on_load)
+
+    def _set_packed(self, dev, P):
+        self._packed, self._packed_dev, self._derived = P, _device(dev), {}
+        self._epoch = next(_clock)
+        return P
+
+    def _covers(self, **want):
+        """Whether `_packed` serves a forward that asks for `want` (pack()'s keyword arguments)."""
+        return True
+
+    def packed(self, dev, **want):
+        if self._packed is None or self._packed_dev != _device(dev) or not self._covers(**want):
+            self.pack(dev, **want)
+        return self._packed
+
+    def derived(self, key, build):
+        if key not in self._derived:
+            self._derived[key] = build()
+        return self._derived[key]
+
+    def invalidate(self):
+        self._packed, self._packed_dev, self._derived = None, None, {}
+        self._epoch = next(_clock)
+
+
+def state_epoch(*roots):
+    """The latest stamp among the PackedState modules under `roots`: it grows whenever one of them packs or is invalidated,
+    and no value comes back - so whatever holds pointers into packed tensors (a captured graph) compares it to know they live."""
+    return max((m._epoch for r in roots for m in r.modules() if isinstance(m, PackedState)), default=0)
 
 
 def weight_norm_weight(sd: Dict[str, torch.Tensor], prefix: str) -> torch.Tensor:

@@ -12,6 +12,7 @@ from typing import Optional
 import torch
 
 from . import ops
+from .packing import state_epoch
 
 
 class GraphCache:
@@ -19,14 +20,24 @@ class GraphCache:
     An eager batch costs ~900 launches x ~10 us of host time - more than the GPU needs for a small batch - so the CLIs and
     servers route their device part through this; `bench.py` captures its fixed shape itself.  Inputs are copied into the
     capture's static tensors; the returned tensors are the capture's static outputs (valid until the next call with the
-    same signature).  At most `max_entries` captures are kept (least recently used dropped: its private memory pool goes with it)."""
+    same signature).  At most `max_entries` captures are kept (least recently used dropped: its private memory pool goes with it).
+    A capture holds raw pointers into the packed weights `fn` reads: `state`, when given, is a callable whose value changes
+    whenever those are rebuilt (`packing.state_epoch` of the models), and a changed value drops every capture."""
 
-    def __init__(self, fn, max_entries: int = 8):
-        self.fn, self.max_entries = fn, max_entries
+    def __init__(self, fn, max_entries: int = 8, state=None):
+        self.fn, self.max_entries, self.state = fn, max_entries, state
         self.entries = {}
         self.captures = 0
+        self._state_seen = None
+
+    def _drop_if_state_changed(self):
+        s = self.state() if self.state is not None else None
+        if s != self._state_seen:
+            self.entries.clear()
+            self._state_seen = s
 
     def __call__(self, *tensors):
+        self._drop_if_state_changed()
         key = tuple((tuple(t.shape), t.dtype) if t is not None else None for t in tensors)
         e = self.entries.get(key)
         if e is None:
@@ -38,6 +49,7 @@ class GraphCache:
                 self.fn(*static_in)
             torch.cuda.current_stream().wait_stream(side)
             torch.cuda.synchronize()
+            self._drop_if_state_changed()            # the warm-up packed: that is the state the capture below belongs to
             g = torch.cuda.CUDAGraph()
             with torch.cuda.graph(g):
                 out = self.fn(*static_in)
@@ -75,11 +87,9 @@ class LipToSpeechPipeline:
         self.repeat_text = int(os.environ.get("REPEAT_TEXT_LABELS", "0")) != 0
 
     def _shared_state_key(self, dev, T):
-        """Identity of the lazily built state sub-batches share: device, frames per clip and the packed-weight object of every
-        module that has one (a reload replaces those objects, so the key changes with them)."""
-        ids = tuple(id(m._packed) for root in (self.model, self.vocoder) for m in root.modules()
-                    if getattr(m, "_packed", None) is not None)
-        return (str(dev), int(T), ids)
+        """Identity of the lazily built state sub-batches share: device, frames per clip and the packed-state epoch of the two
+        models (it moves whenever a module under them packs or drops its weights, and never returns to an earlier value)."""
+        return (str(dev), int(T), state_epoch(self.model, self.vocoder))
 
     @torch.no_grad()
     def stage1_device(self, video, padding_mask, spk_emb):

@@ -12,6 +12,7 @@ import torch.nn as nn
 
 from . import ops
 from .ops import ACT_NONE, ACT_PRELU, ACT_SWISH, F_RES_PRE, MODE_CONV2D
+from .packing import PackedState
 
 
 def _fold_bn(bn: nn.Module):
@@ -105,7 +106,7 @@ class ResNet(nn.Module):
         return nn.Sequential(*mods)
 
 
-class ResEncoder(nn.Module):
+class ResEncoder(nn.Module, PackedState):
     """avhubert/resnet.py:131-169.  forward(x[B,1,T,88,88]) -> [B,512,T]."""
 
     def __init__(self, relu_type="prelu", weights=None, dtype=ops.F16):
@@ -122,7 +123,7 @@ class ResEncoder(nn.Module):
         self.relu_type = relu_type
         self.dtype = dtype
         self.u8_transform = (88, 0.421, 0.165)   # image_crop_size / image_mean / image_std (hubert_pretraining.py config)
-        self._packed = None
+        self._init_packed()
 
     # ---- packing -------------------------------------------------------------------------------------------------
     def _slopes(self, mod, n, dev):
@@ -131,7 +132,7 @@ class ResEncoder(nn.Module):
         return torch.zeros(n, device=dev)  # ReLU == PReLU with slope 0
 
     def pack(self, device=None):
-        """Fold eval-mode BatchNorm into 16-bit [N, taps*Cin] weights + fp32 bias; call again after loading weights."""
+        """Fold eval-mode BatchNorm into 16-bit [N, taps*Cin] weights + fp32 bias."""
         dev = torch.device(device) if device is not None else self.frontend3D[0].weight.device
         t16 = ops.torch_dtype(self.dtype)
         P = {}
@@ -166,13 +167,8 @@ class ResEncoder(nn.Module):
                         e["ba"] = (e["b2"] + e["bd"]).contiguous()
                 blocks.append(e)
         P["blocks"] = blocks
-        self._packed = P
+        self._set_packed(dev, P)
         return self
-
-    def load_state_dict(self, *a, **k):
-        r = super().load_state_dict(*a, **k)
-        self._packed = None
-        return r
 
     # ---- forward -------------------------------------------------------------------------------------------------
     def forward_rows(self, x):
@@ -183,9 +179,7 @@ class ResEncoder(nn.Module):
             x = x[:, 0]
         B, T, H, W = x.shape
         x = x.contiguous()
-        if self._packed is None or self._packed["stem_w"].device != x.device:
-            self.pack(x.device)
-        P, dt = self._packed, self.dtype
+        P, dt = self.packed(x.device), self.dtype
         t16 = ops.torch_dtype(dt)
         dev = x.device
         N = B * T

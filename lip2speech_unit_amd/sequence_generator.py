@@ -17,6 +17,7 @@ from typing import Dict, List, Optional
 import torch
 
 from . import ops
+from .packing import state_epoch
 
 
 class MultiTargetSequenceGenerator:
@@ -107,7 +108,7 @@ class MultiTargetSequenceGenerator:
         if self.use_hipgraph:
             from .pipeline import GraphCache
             if self._graphs is None:
-                self._graphs = GraphCache(self._device_part)
+                self._graphs = GraphCache(self._device_part, state=lambda: state_epoch(self.model))
             Bv, Tv = video.shape[0], video.shape[2] if video.dim() == 5 else video.shape[1]
             Tp = -(-Tv // self.frame_bucket) * self.frame_bucket
             pm = padding_mask if padding_mask is not None else torch.zeros(Bv, Tv, dtype=torch.bool, device=video.device)

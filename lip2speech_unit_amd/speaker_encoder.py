@@ -22,6 +22,7 @@ import torch.nn as nn
 
 from . import audio, ops, weights
 from ._lib import L2SError
+from .packing import PackedState
 
 SAMPLING_RATE = 16000
 MEL_N_FFT, MEL_HOP, MEL_N_CHANNELS = 400, 160, 40      # 25 ms window, 10 ms step
@@ -116,7 +117,7 @@ def synthetic_state_dict(seed=0):
     return sd
 
 
-class SpeakerEncoder(nn.Module):
+class SpeakerEncoder(nn.Module, PackedState):
     """Parameter holder with RTVC's state dict names (lstm.*, linear.*, similarity_weight / similarity_bias are accepted and
     ignored); `embed` runs the device path."""
 
@@ -125,14 +126,13 @@ class SpeakerEncoder(nn.Module):
         self.lstm = nn.LSTM(MEL_N_CHANNELS, HIDDEN, LAYERS, batch_first=True)
         self.linear = nn.Linear(HIDDEN, EMBED)
         self.mel = PowerMel()
-        self._packed = {}
+        self._init_packed()
 
     def load_state_dict(self, sd, strict=True):
         sd = {k: v for k, v in sd.items() if k not in ("similarity_weight", "similarity_bias")}
         w = sd.get("lstm.weight_hh_l0")
         if w is not None and tuple(w.shape) != (4 * HIDDEN, HIDDEN):
             raise ValueError(f"speaker encoder: hidden size {w.shape[-1]} is not supported (the device path is built for {HIDDEN})")
-        self._packed = {}
         return super().load_state_dict(sd, strict=strict)
 
     def load_checkpoint(self, path):
@@ -142,19 +142,20 @@ class SpeakerEncoder(nn.Module):
         return self
 
     def pack(self, dev):
-        """The device operands, built once per device: [(w_ih_p, bias_p, w_hh_p)] * 3, linear weight transposed, linear bias."""
+        """The device operands, built once per device (derived state keyed by the device index, so a process that alternates
+        devices keeps both sets): [(w_ih_p, bias_p, w_hh_p)] * 3, linear weight transposed, linear bias."""
         dev = torch.device(dev)
         if dev.type != "cuda":
             raise L2SError("the speaker encoder needs a HIP device (there is no CPU path)")
-        key = dev.index if dev.index is not None else torch.cuda.current_device()
-        if key not in self._packed:
+
+        def build():
             layers = []
             for l in range(LAYERS):
                 ps = [getattr(self.lstm, f"{n}_l{l}") for n in ("weight_ih", "weight_hh", "bias_ih", "bias_hh")]
                 layers.append(tuple(t.to(dev) for t in pack_lstm_layer(*[p.detach().cpu() for p in ps])))
-            self._packed[key] = (layers, self.linear.weight.detach().float().t().contiguous().to(dev),
-                                 self.linear.bias.detach().float().contiguous().to(dev))
-        return self._packed[key]
+            return (layers, self.linear.weight.detach().float().t().contiguous().to(dev),
+                    self.linear.bias.detach().float().contiguous().to(dev))
+        return self.derived(dev.index if dev.index is not None else torch.cuda.current_device(), build)
 
     def hidden_last(self, xproj0, row_off, packed_layers, max_seqs=2560):
         """Final hidden state of layer 2 for the sequences row_off (int32 host array: first row of each 160-step window in

@@ -20,6 +20,7 @@ from . import ops
 from ._lib import L2SError
 from .hubert import TransformerEncoder
 from .ops import ACT_GELU, F_DUAL, F_MASK, MODE_CONV1D
+from .packing import PackedState
 
 CONV_LAYERS = ((512, 10, 5), (512, 3, 2), (512, 3, 2), (512, 3, 2), (512, 3, 2), (512, 2, 2), (512, 2, 2))   # (dim, k, stride)
 MIN_SAMPLES = 400          # the receptive field of one feature frame
@@ -67,7 +68,7 @@ class HubertConfig:
         return c
 
 
-class ConvFeatureExtractionModel(nn.Module):
+class ConvFeatureExtractionModel(nn.Module, PackedState):
     """fairseq ConvFeatureExtractionModel(mode="default"): parameters conv_layers.{i}.0.weight and conv_layers.0.2.{weight,bias}."""
 
     def __init__(self, mode="default", dtype=ops.F32):
@@ -84,7 +85,7 @@ class ConvFeatureExtractionModel(nn.Module):
                 self.conv_layers.append(nn.Sequential(conv, nn.Dropout(0.0), nn.GELU()))
             cin = dim
         self.dtype = dtype
-        self._packed = None
+        self._init_packed()
 
     def pack(self, dev):
         t16 = ops.torch_dtype(self.dtype)
@@ -94,15 +95,13 @@ class ConvFeatureExtractionModel(nn.Module):
              # Conv1d weight [Cout, Cin, k] -> the tap-GEMM's [Cout, k * Cin] (tap-major)
              "w": [L[0].weight.detach().float().permute(0, 2, 1).reshape(L[0].weight.shape[0], -1).to(dev, t16).contiguous()
                    for L in list(self.conv_layers)[1:]]}
-        self._packed = P
+        self._set_packed(dev, P)
 
     def forward_rows(self, wav, n_samples):
         """wav: device [B, S] fp32 in (-1, 1) or int16 PCM; n_samples: host list of clip lengths.  Returns (rows [B*T, 512] of the
         operand type - clip b's rows past num_frames(n_b) are padding, not zeros -, T)."""
         dev = wav.device
-        if self._packed is None or self._packed["g0"].device != dev:
-            self.pack(dev)
-        P, dt = self._packed, self.dtype
+        P, dt = self.packed(dev), self.dtype
         t16 = ops.torch_dtype(dt)
         B, S = wav.shape
         C = CONV_LAYERS[0][0]
@@ -122,7 +121,7 @@ class ConvFeatureExtractionModel(nn.Module):
         return x, T
 
 
-class HubertModel(nn.Module):
+class HubertModel(nn.Module, PackedState):
     """Inference subset of fairseq's HubertModel: extract_features(source, output_layer) with padding handled per clip."""
 
     def __init__(self, cfg: HubertConfig = None, dtype=ops.F32):
@@ -143,24 +142,20 @@ class HubertModel(nn.Module):
         self.post_extract_proj = nn.Linear(self.embed, cfg.encoder_embed_dim)
         self.encoder = TransformerEncoder(cfg, dtype=dtype)
         self.dtype = dtype
-        self._packed = None
+        self._init_packed()
 
     def load_state_dict(self, state_dict, strict=True, **kw):
         sd = {k: v for k, v in state_dict.items() if not k.startswith(IGNORED_KEYS)}
-        r = super().load_state_dict(sd, strict=strict, **kw)
-        self._packed = None
-        self.encoder._packed = None
-        self.feature_extractor._packed = None
-        return r
+        return super().load_state_dict(sd, strict=strict, **kw)
 
     def pack(self, dev):
         t16 = ops.torch_dtype(self.dtype)
-        self._packed = {
+        self._set_packed(dev, {
             "ln": (self.layer_norm.weight.detach().float().to(dev).contiguous(),
                    self.layer_norm.bias.detach().float().to(dev).contiguous()),
             "wpe": self.post_extract_proj.weight.detach().to(dev, t16).contiguous(),
             "bpe": self.post_extract_proj.bias.detach().float().to(dev).contiguous(),
-        }
+        })
 
     def extract_rows(self, source, n_samples=None, output_layer=None):
         """source: device [B, S] fp32 or int16.  Returns (fp32 [B*T, d] rows (b, t), lens int32 [B] on the device, host lens, B, T)."""
@@ -175,9 +170,7 @@ class HubertModel(nn.Module):
         if len(ns) != B or any(v < MIN_SAMPLES or v > S for v in ns):
             raise ValueError(f"n_samples: every clip needs {MIN_SAMPLES} <= n <= {S} samples, got {ns}")
         dev = source.device
-        if self._packed is None or self._packed["bpe"].device != dev:
-            self.pack(dev)
-        P, dt = self._packed, self.dtype
+        P, dt = self.packed(dev), self.dtype
         t16 = ops.torch_dtype(dt)
         d = self.cfg.encoder_embed_dim
         feat, T = self.feature_extractor.forward_rows(source, ns)

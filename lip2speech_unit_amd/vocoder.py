@@ -16,7 +16,7 @@ import torch.nn as nn
 
 from . import ops
 from .ops import ACT_GELU, ACT_LRELU, F_ACCUM, F_DUAL, F_MASK, F_RES_POST, MODE_CONV1D
-from .packing import convtranspose_fused, convtranspose_phases, pack_conv1d
+from .packing import PackedState, convtranspose_fused, convtranspose_phases, pack_conv1d
 
 LRELU_SLOPE = 0.1  # speech-resynthesis/models.py:13
 # C = 64 / 128 stages: one launch per (c1, c2) conv pair out of LDS (csrc/respair.hip); 0 = the unfused tap-GEMM pairs (A/B)
@@ -88,7 +88,7 @@ class ResBlock1(nn.Module):
             m.remove_weight_norm()
 
 
-class Generator(nn.Module):
+class Generator(nn.Module, PackedState):
     """speech-resynthesis/models.py:72-122."""
 
     def __init__(self, h, dtype=ops.F16):
@@ -112,7 +112,7 @@ class Generator(nn.Module):
                 self.resblocks.append(ResBlock1(h, ch, k, d))
         self.conv_post = _WN((1, ch, 7), 1, 1)
         self.dtype = dtype
-        self._packed = None
+        self._init_packed()
 
     def remove_weight_norm(self):
         for m in self.ups:
@@ -121,12 +121,7 @@ class Generator(nn.Module):
             m.remove_weight_norm()
         self.conv_pre.remove_weight_norm()
         self.conv_post.remove_weight_norm()
-        self._packed = None
-
-    def load_state_dict(self, *a, **k):
-        r = super().load_state_dict(*a, **k)
-        self._packed = None
-        return r
+        self.invalidate()
 
     # ---- packing -------------------------------------------------------------------------------------------------
     def _conv_pre_weight(self):
@@ -207,13 +202,14 @@ class Generator(nn.Module):
         P["post_b"] = float(self.conv_post.bias.detach().float()[0])
         return P
 
+    def _precise_state(self, dev):
+        return self.derived(("precise", torch.device(dev)), lambda: self._pack_precise(dev))
+
     def generator_rows_precise(self, cat32, lens, B, T0, base_mul):
         """speech-resynthesis/models.py:98-114 at reference precision (see _PreciseOps).  cat32: fp32 [B*T0, Cin] generator
         input rows; returns (wav fp32 [B, T0*160], pcm int16)."""
         dev = cat32.device
-        if getattr(self, "_packed_precise", None) is None or self._packed_precise["pre_b"].device != dev:
-            self._packed_precise = self._pack_precise(dev)
-        P, po = self._packed_precise, _PreciseOps(self.dtype, dev)
+        P, po = self._precise_state(dev), _PreciseOps(self.dtype, dev)
         Cin, c0 = cat32.shape[1], P["pre_b"].shape[0]
         T, mul = T0, base_mul
         a = po.split(cat32, B, T, Cin, lens=lens, len_mul=mul)
@@ -492,7 +488,7 @@ class MelCodeGenerator(Generator):
             P["t_table"] = table.to(dev, t16).contiguous()
             P["t_phases"] = [dict(ph, w=ph["w"].to(dev, t16).contiguous()) for ph in convtranspose_phases(cw, 2, 1)]
             P["t_up_b"], P["t_fc_w"], P["t_fc_b"] = cb.to(dev), fw.to(dev, t16).contiguous(), fb.to(dev)
-        self._packed = P
+        self._set_packed(dev, P)
 
     def _check_text(self, t):
         if self.text_supervision and t is None:
@@ -523,6 +519,23 @@ class MelCodeGenerator(Generator):
                                    dtype=dt)                                                             # :65,:73
         return self._rows(fill, spkr, lens, 1, B, L, dev, text)
 
+    def _precise_front(self, dev):
+        """The (hi, lo) weights of the layers in front of the generator, for forward_rows_precise."""
+        def build():
+            t16, ct = ops.torch_dtype(self.dtype), self.layer[0]
+            F = {
+                "up": [dict(ph, w=_hi_lo(ph["w"], t16, dev)) for ph in convtranspose_phases(ct.weight.detach().float(), 2, 1)],
+                "up_b": ct.bias.detach().float().to(dev).contiguous(),
+                "fc": _hi_lo(self.fc.weight, t16, dev), "fc_b": self.fc.bias.detach().float().to(dev).contiguous(),
+                "sp": _hi_lo(self.spkr.weight, t16, dev), "sp_b": self.spkr.bias.detach().float().to(dev).contiguous()}
+            if self.text_supervision:
+                table, cw, cb, fw, fb = self._text_weights()
+                F.update(
+                    t_table=table.to(dev), t_up=[dict(ph, w=_hi_lo(ph["w"], t16, dev)) for ph in convtranspose_phases(cw, 2, 1)],
+                    t_up_b=cb.to(dev), t_fc=_hi_lo(fw, t16, dev), t_fc_b=fb.to(dev))
+            return F
+        return self.derived(("precise_front", torch.device(dev)), build)
+
     def forward_rows_precise(self, code, mel, spkr, lens=None, t_label=None):
         """forward_rows at reference precision (parity switch, see _PreciseOps): models_multi_input.py:60-97 with every Linear /
         ConvTranspose as three hi / lo tap-GEMM launches; embedding lookup, concatenation and the layout transposes are torch
@@ -535,19 +548,7 @@ class MelCodeGenerator(Generator):
         if lens is None:
             lens = torch.full((B,), L, device=dev, dtype=torch.int32)
         po = _PreciseOps(self.dtype, dev)
-        if getattr(self, "_front_precise", None) is None or self._front_precise["up_b"].device != dev:
-            ct = self.layer[0]
-            self._front_precise = {
-                "up": [dict(ph, w=_hi_lo(ph["w"], t16, dev)) for ph in convtranspose_phases(ct.weight.detach().float(), 2, 1)],
-                "up_b": ct.bias.detach().float().to(dev).contiguous(),
-                "fc": _hi_lo(self.fc.weight, t16, dev), "fc_b": self.fc.bias.detach().float().to(dev).contiguous(),
-                "sp": _hi_lo(self.spkr.weight, t16, dev), "sp_b": self.spkr.bias.detach().float().to(dev).contiguous()}
-            if self.text_supervision:
-                table, cw, cb, fw, fb = self._text_weights()
-                self._front_precise.update(
-                    t_table=table.to(dev), t_up=[dict(ph, w=_hi_lo(ph["w"], t16, dev)) for ph in convtranspose_phases(cw, 2, 1)],
-                    t_up_b=cb.to(dev), t_fc=_hi_lo(fw, t16, dev), t_fc_b=fb.to(dev))
-        F = self._front_precise
+        F = self._precise_front(dev)
         Ct = self._text_dims()[1] if self.text_supervision else 0
         Cin = nm + 2 * E + Ct
         emb = self.dict.weight.detach().float().to(dev)[code.long()].reshape(B * L, E).contiguous()           # :67
@@ -605,9 +606,7 @@ class MelCodeGenerator(Generator):
     def _rows(self, fill, spkr, lens, lm, B, L, dev, text=None):
         """models_multi_input.py:60-97 on channels-last rows.  `fill(P, cat, emb, Cin, dt)` writes the unit embeddings and the
         mel columns of the concat buffer; `lens` counts units of 1 / lm code frames (lm = 1: code frames, 2: video frames)."""
-        if self._packed is None or self._packed["table"].device != dev:
-            self.pack(dev)
-        P, dt, h = self._packed, self.dtype, self.h
+        P, dt, h = self.packed(dev), self.dtype, self.h
         t16 = ops.torch_dtype(dt)
         E, nm = h.embedding_dim, self.num_mels
         T0 = 2 * L
