@@ -734,6 +734,45 @@ int l2s_lstm_layer(const float* xproj, int ldx, int64_t n_rows, const int32_t* r
 int l2s_spk_embed_head(const float* h_last, int n_rows, const int32_t* first, const int32_t* count, const float* w_t,
                        const float* bias, int B, int hidden, float* out, void* stream);
 
+/*
+ * Mouth ROIs from raw frames and 68-point landmarks: what avhubert/preparation/align_mouth.py:33-44 (warp_img / apply_transform:
+ * skimage estimate_transform('similarity') + tf.warp), :63-87 (cut_patch) and :130-181 (crop_patch: the forward window of
+ * landmarks, the tail rule) compute per frame on the host, and what the reference's server repeats on every request
+ * (server.py:268-269, get_mouth_frames).  The algorithm is restated in DESIGN.md section 19; the host class is
+ * lip2speech_unit_amd/mouth_roi.py, csrc/mouthroi.hip holds both entries.  All geometry is fp64; neither entry uses an atomic or
+ * synchronises with the host, and a frame's bytes do not depend on the other clips of the batch.
+ *
+ * l2s_mouth_transforms - per clip b = rows [first[b], first[b] + count[b]) (clamped to [0, N)) of landmarks, T = count[b],
+ *   margin = min(T, window_margin); for frame t of the clip:
+ *   landmarks: fp64 [N, L, 2] (x, y); mean_face: fp64 [L, 2]; stable_ids: int32 [n_stable] (clamped to [0, L); n_stable <= 16);
+ *   src = the mean over frames min(t, T - margin) .. + margin - 1 of the stable landmarks (a window looks forward and never leaves
+ *   its clip; the last margin - 1 frames reuse the last full window's transform), dst = the mean face at the same ids;
+ *   M = Umeyama's similarity src -> dst in its 2-D closed form: A = dst_c^T src_c / n, p = A00 + A11, q = A10 - A01, r = hypot(p, q),
+ *   rotation [[p, -q], [q, p]] / r, scale r / (sum of the per-axis variances of src, ddof 0), translation dst_mean - s R src_mean;
+ *   (cx, cy) = the mean of frame t's own landmarks [start_idx, stop_idx) through M, clamped in align_mouth.py's order
+ *   (cy - crop_h/2 < 0 -> crop_h/2, then x, then cy + crop_h/2 > std_h -> std_h - crop_h/2, then x);
+ *   inv: fp64 [N, 6] = the 2 x 3 matrix of M^-1, row-major; origin: int32 [N, 2] = (x0, y0) = (rint(cx) - crop_w/2, rint(cy) - crop_h/2),
+ *   rint rounding half to even.  Rows of inv / origin that belong to no clip are not written.  Stable points of zero variance
+ *   give NaN in inv (and origin 0): the host class reports them.
+ * l2s_mouth_warp - per frame n, the crop_h x crop_w window at origin[n] of tf.warp(frame, inverse_map = inv[n], order 1,
+ *   mode 'constant', cval 0), times 255, truncated to uint8; nothing outside the window is computed:
+ *   frames: uint8 [N, H, W, C], C = 1 or 3 (any address); the output pixel (x, y) = (x0 + i, y0 + j) samples the source at
+ *   (sx, sy) = ((inv0 x + inv1 y) + inv2, (inv3 x + inv4 y) + inv5), bilinearly over the four neighbours of (floor sx, floor sy) as
+ *   ((1 - dy) ((1 - dx) tl + dx tr) + dy ((1 - dx) bl + dx br)) of the values u8 / 255.0, a neighbour outside the frame counting as
+ *   0; every product and sum is rounded on its own (no fused multiply-add), channels independently;
+ *   roi: NULL or uint8 [N, crop_h, crop_w, C]; gray: NULL or uint8 [N, crop_h, crop_w] = cv2's 8-bit BGR2GRAY
+ *   (1868 B + 9617 G + 4899 R + 8192) >> 14 of the truncated ROI (C = 1: the ROI itself);
+ *   model_in: NULL or fp32 [N, model_crop, model_crop] = ((gray / 255.0f) - mean) / std with fp32 divisions over the centre crop
+ *   at offset (crop - model_crop) / 2 - hubert_dataset.py:242-245, bit-identical to numpy.  At least one output is needed; an
+ *   output passed as NULL is not written.  roi, gray and model_in must be 4-byte aligned, inv 8-byte aligned.
+ *   Supported: C in {1, 3}, H, W <= 32768, crop_h, crop_w <= 4096; anything else returns L2S_EUNSUPPORTED.
+ */
+int l2s_mouth_transforms(const double* landmarks, int N, int L, const int32_t* first, const int32_t* count, int B,
+                         const double* mean_face, const int32_t* stable_ids, int n_stable, int window_margin, int std_h, int std_w,
+                         int crop_h, int crop_w, int start_idx, int stop_idx, double* inv, int32_t* origin, void* stream);
+int l2s_mouth_warp(const uint8_t* frames, int N, int H, int W, int C, const double* inv, const int32_t* origin, int crop_h, int crop_w,
+                   uint8_t* roi, uint8_t* gray, float* model_in, int model_crop, float mean, float std, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -134,6 +134,8 @@ SIGNATURES = {
     "l2s_stft_mel_power": ([_vp, _i, ctypes.c_int64, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp], _i),
     "l2s_lstm_layer": ([_vp, _i, ctypes.c_int64, _vp, _vp, _i, _i, _i, _vp, _vp, _vp], _i),
     "l2s_spk_embed_head": ([_vp, _i, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp], _i),
+    "l2s_mouth_transforms": ([_vp, _i, _i, _vp, _vp, _i, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp], _i),
+    "l2s_mouth_warp": ([_vp, _i, _i, _i, _i, _vp, _vp, _i, _i, _vp, _vp, _vp, _i, _f, _f, _vp], _i),
 }
 
 _lib = None

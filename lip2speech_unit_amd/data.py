@@ -61,7 +61,9 @@ class MultiTargetDataset(DatasetBase):
     (inference.py:164-179) can batch it: `num_tokens` / `size` / `ordered_indices` follow hubert_dataset.py:533-552."""
 
     def __init__(self, manifest_path, label_path=None, label_processor=None, pad=1, image_mean=0.421, image_std=0.165,
-                 image_crop_size=88, text_label_path=None):
+                 image_crop_size=88, text_label_path=None, mouth_cropper=None):
+        """mouth_cropper (None: the video path is read with load_video): a callable video path -> gray uint8 [T, 96, 96] mouth
+        ROIs, e.g. mouth_roi.VideoMouthCropper (raw frames + landmarks, cropped on the device)."""
         with open(manifest_path) as f:
             self.root = f.readline().strip()
             rows = [ln.rstrip("\n").split("\t") for ln in f if ln.strip()]
@@ -84,6 +86,7 @@ class MultiTargetDataset(DatasetBase):
         self.label_processors = [label_processor]
         self.pad = pad
         self.mean, self.std, self.crop = image_mean, image_std, image_crop_size
+        self.mouth_cropper = mouth_cropper
 
     def __len__(self):
         return len(self.ids)
@@ -103,7 +106,8 @@ class MultiTargetDataset(DatasetBase):
 
     def __getitem__(self, index):
         video_fn = self.names[index][0]
-        frames = load_video(os.path.join(self.root, video_fn))
+        path = os.path.join(self.root, video_fn)
+        frames = load_video(path) if self.mouth_cropper is None else np.asarray(self.mouth_cropper(path))
         feats = normalize_frames(frames, self.crop, self.mean, self.std)
         sample = {"id": index, "fid": self.ids[index], "names": self.names[index],
                   "video_source": torch.from_numpy(np.ascontiguousarray(feats)), "audio_source": None}

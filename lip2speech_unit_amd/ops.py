@@ -1023,6 +1023,53 @@ def spk_embed_head(h_last, first, count, w_t, bias, out, *, B, n_rows=None, hidd
         flops=2.0 * n_rows * hidden * hidden, nbytes=4.0 * (n_rows + B + hidden) * hidden)
 
 
+def mouth_transforms(landmarks, first, count, mean_face, stable_ids, inv, origin, *, B, window_margin=12, std_h=256, std_w=256,
+                     crop_h=96, crop_w=96, start_idx=48, stop_idx=68):
+    """Per-frame similarity transforms of the mouth cropper (csrc/mouthroi.hip): landmarks fp64 [N, L, 2], clip b = rows
+    [first[b], first[b] + count[b]) (int32 [B]), mean_face fp64 [L, 2], stable_ids int32 [n_stable] -> inv fp64 [N, 6] (the 2 x 3
+    inverse map) and origin int32 [N, 2] (x0, y0 of the crop window in the std_h x std_w aligned image)."""
+    _req(landmarks, torch.float64, "landmarks"), _req(mean_face, torch.float64, "mean_face"), _req(inv, torch.float64, "inv")
+    for t, n in ((first, "first"), (count, "count"), (stable_ids, "stable_ids"), (origin, "origin")):
+        _req(t, torch.int32, n)
+    if landmarks.dim() != 3 or landmarks.shape[2] != 2 or not landmarks.is_contiguous():
+        raise L2SError("mouth_transforms: landmarks must be dense [N, L, 2]")
+    N, L = landmarks.shape[0], landmarks.shape[1]
+    if not mean_face.is_contiguous() or tuple(mean_face.shape) != (L, 2):
+        raise L2SError("mouth_transforms: mean_face must be dense [L, 2]")
+    if min(first.numel(), count.numel()) < B or not inv.is_contiguous() or inv.numel() < 6 * N or not origin.is_contiguous() or origin.numel() < 2 * N:
+        raise L2SError("mouth_transforms: first / count [B], inv dense [N, 6], origin dense [N, 2]")
+    _run("l2s_mouth_transforms", lambda: _lib.load().l2s_mouth_transforms(
+        _ptr(landmarks), N, L, _ptr(first), _ptr(count), B, _ptr(mean_face), _ptr(stable_ids), stable_ids.numel(), window_margin,
+        std_h, std_w, crop_h, crop_w, start_idx, stop_idx, _ptr(inv), _ptr(origin), _stream()),
+        nbytes=16.0 * N * L + 56.0 * N)
+
+
+def mouth_warp(frames, inv, origin, *, crop_h=96, crop_w=96, roi=None, gray=None, model_in=None, model_crop=88, mean=0.421, std=0.165):
+    """The crop window of every frame's aligned image (csrc/mouthroi.hip): frames uint8 [N, H, W, C] (C 1 or 3) or [N, H, W], inv
+    fp64 [N, 6], origin int32 [N, 2] -> roi uint8 [N, crop_h, crop_w, C], gray uint8 [N, crop_h, crop_w] and / or model_in fp32
+    [N, model_crop, model_crop]; an output left None is not written."""
+    _req(frames, torch.uint8, "frames"), _req(inv, torch.float64, "inv"), _req(origin, torch.int32, "origin")
+    if frames.dim() not in (3, 4) or not frames.is_contiguous():
+        raise L2SError("mouth_warp: frames must be dense [N, H, W, C] or [N, H, W]")
+    N, H, W = frames.shape[:3]
+    C = frames.shape[3] if frames.dim() == 4 else 1
+    if not inv.is_contiguous() or inv.numel() < 6 * N or not origin.is_contiguous() or origin.numel() < 2 * N:
+        raise L2SError("mouth_warp: inv dense [N, 6], origin dense [N, 2]")
+    if roi is None and gray is None and model_in is None:
+        raise L2SError("mouth_warp: roi, gray or model_in is needed")
+    for t, dt, n, need in ((roi, torch.uint8, "roi", N * crop_h * crop_w * C), (gray, torch.uint8, "gray", N * crop_h * crop_w),
+                           (model_in, torch.float32, "model_in", N * model_crop * model_crop)):
+        if t is not None:
+            _req(t, dt, n)
+            if not t.is_contiguous() or t.numel() < need:
+                raise L2SError(f"mouth_warp: {n} must be dense with at least {need} elements")
+    out_bytes = sum(t.numel() * t.element_size() for t in (roi, gray, model_in) if t is not None)
+    _run("l2s_mouth_warp", lambda: _lib.load().l2s_mouth_warp(
+        _ptr(frames), N, H, W, C, _ptr(inv), _ptr(origin), crop_h, crop_w, _ptr(roi), _ptr(gray), _ptr(model_in), model_crop,
+        float(mean), float(std), _stream()),
+        flops=14.0 * N * crop_h * crop_w * C, nbytes=float(out_bytes) + 4.0 * N * crop_h * crop_w * C, shape=f"N{N} {H}x{W}x{C}")
+
+
 # ---- torch.library registration ("PyTorch-ROCm custom ops", SURVEY 8b last row) --------------------------------------------------
 # Every launcher above is ALSO a dispatcher-visible operator `torch.ops.lip2speech.<name>` (schema below, CUDA = HIP kernel only: a
 # CPU tensor finds no kernel and raises; a fake / meta implementation gives shapes to torch.compile and fake-tensor tracing), and
@@ -1144,6 +1191,11 @@ _SCHEMAS = {
                   "Tensor(a!)? h_seq=None, Tensor(b!)? h_last=None) -> ()",
     "spk_embed_head": "(Tensor h_last, Tensor first, Tensor count, Tensor w_t, Tensor bias, Tensor(a!) out, *, int B, "
                       "int? n_rows=None, int hidden=256) -> ()",
+    "mouth_transforms": "(Tensor landmarks, Tensor first, Tensor count, Tensor mean_face, Tensor stable_ids, Tensor(a!) inv, "
+                        "Tensor(b!) origin, *, int B, int window_margin=12, int std_h=256, int std_w=256, int crop_h=96, int crop_w=96, "
+                        "int start_idx=48, int stop_idx=68) -> ()",
+    "mouth_warp": "(Tensor frames, Tensor inv, Tensor origin, *, int crop_h=96, int crop_w=96, Tensor(a!)? roi=None, "
+                  "Tensor(b!)? gray=None, Tensor(c!)? model_in=None, int model_crop=88, float mean=0.421, float std=0.165) -> ()",
 }
 # C-ABI entry each operator launches (tests/test_torchlib_cpu.py: every device entry of include/lip2speech_hip.h has a twin)
 ENTRY_OF = {n: "l2s_" + n for n in _SCHEMAS}
