@@ -773,6 +773,69 @@ int l2s_mouth_transforms(const double* landmarks, int N, int L, const int32_t* f
 int l2s_mouth_warp(const uint8_t* frames, int N, int H, int W, int C, const double* inv, const int32_t* origin, int crop_h, int crop_w,
                    uint8_t* roi, uint8_t* gray, float* model_in, int model_crop, float mean, float std, void* stream);
 
+/*
+ * One autoregressive decoder step against a key/value cache: the hot path of the Whisper speech recogniser the reference runs on
+ * every synthesis request (server.py:48 `WhisperASR(model='base.en', ...)`, server.py:337-342 `asr.run(pred_audio_path)`), i.e.
+ * of openai-whisper's greedy decoding (third-party; the arithmetic is restated in DESIGN.md section 20).  csrc/whisper_decode.hip
+ * holds the three entries.  Whatever changes from step to step is read from DEVICE int32 scalars, never passed by value: a step
+ * is a fixed launch sequence and can be replayed from a captured graph.  No atomics, every reduction in a fixed order: a clip's
+ * bytes do not depend on its batch mates or on the run.
+ *
+ * l2s_kv_attention - one query per (clip, head) against a cache, heads 64 wide:
+ *   q: 16-bit [B, ldq], head h = columns 64 h .. 64 h + 63, ALREADY scaled; k_cache / v_cache: 16-bit dense [B, cache_T, 64 H];
+ *   n = the valid length: pos == NULL: n_valid (cross-attention: the encoder's 1500 rows); else p = pos[b * pos_stride]
+ *   (pos_stride 0: one position for the batch, 1: per clip) and n = p + 1, clamped to [0, cache_T];
+ *   k_new / v_new (both or neither; need pos): 16-bit [B, ld_new]; when 0 <= p < cache_T the rows are first stored at cache row p,
+ *   and nothing else of the caches is written;
+ *   out[b, 64 h + c] = sum_j softmax_j(q_bh . k_bjh) v_bjhc over j < n: fp32 dot products, fp32 online softmax (v_exp_f32),
+ *   keys split over 128 lane groups of a block whose partials are merged in a fixed order, one rounding to 16 bits; n = 0 gives
+ *   zeros.  Cache rows at or past n are never read (they may hold anything).
+ *   Supported: 64 H <= 1280, cache_T <= 1500, B <= 65535; ldq, ldo, ld_new multiples of 8, pointers 16-byte aligned.
+ * l2s_vocab_argmax - the tied output layer with the greedy choice fused in:
+ *   x: 16-bit [B, ldx] (d used), emb: 16-bit [V, lde] (the token embedding); logit[b, v] = x_b . emb_v on the 16x16x32 MFMA, fp32
+ *   accumulation, k ascending in steps of 32;  suppress / begin_suppress: NULL or uint8 [V], nonzero = the id may not be chosen;
+ *   begin_suppress applies only when *step == first_step (step: device int32; needed with begin_suppress);
+ *   token[b] = argmax over the allowed ids, the smallest id on a tie (-1 when none is allowed); logprob[b] = that logit's log
+ *   softmax over the ALLOWED ids, fp32; logits: NULL or fp32 dense [B, V], the raw logits of every id, suppressed or not.
+ *   Two levels: per 64-row tile a (maximum, first index, sum of exp(logit - maximum)) partial per clip, then a finishing block
+ *   per clip; no [B, V] tensor unless asked for.  workspace: l2s_vocab_argmax_workspace(V, B) bytes (0 = unsupported).
+ *   Supported: V <= 65536 (any value, no multiple of a tile), d a multiple of 64 up to 1280, any B >= 1.
+ * l2s_whisper_advance - the bookkeeping of a step, one block; p = *pos:
+ *   per clip: t = done[b] ? eot : token[b] (an id outside [0, V) counts as eot); token[b] = t; tokens[b, p] = t (int32
+ *   [B, ld_tok]; skipped when p >= ld_tok); while not done: sum_logprob[b] += logprob[b] (the eot's included, as openai-whisper's
+ *   sum_logprobs) and lengths[b] += 1 unless t is eot; done[b] |= (t == eot) (uint8);
+ *   x_next[b, :d] = tok_emb[t] (16-bit [V, lde]) + pos_emb[p + 1] (fp32 dense [n_ctx, d]), fp32 - the next step's row of the
+ *   residual stream; skipped when p + 1 >= n_ctx;  then *pos = p + 1 and *n_active = the number of clips not done.
+ *   Supported: d a multiple of 8 up to 1280, V <= 65536, B <= 65535.
+ */
+/*
+ * l2s_whisper_logmel - Whisper's input features as transformers' WhisperFeatureExtractor (and openai-whisper's
+ *   log_mel_spectrogram + pad_or_trim) define them, csrc/whisper_logmel.hip:
+ *   wav: [B, ldw] int16 (wav_is_i16; x / 32768) or fp32, S <= 480 000 columns used, n_samples[b] (NULL: S) real samples, clamped
+ *   to [0, S]; the clip is zero-extended to 480 000 samples; frame t = samples [160 t - 200, 160 t + 200), t = 0 .. 2999 (the
+ *   3 001st frame is dropped), positions outside [0, 480 000) reflected once; periodic Hann window of 400, power spectrum
+ *   re^2 + im^2 (k-ordered fp32 fma chains on the f32-input MFMA), 80 bands mel[m] = sum_k fb[m, k] P[k], k ascending over
+ *   fb_range[m] = [lo, hi); x = log10(max(mel, 1e-10)); x = max(x, clip_max - 8) with clip_max the maximum over the clip's
+ *   3000 x 80 values (per 32-frame tile, then over the tiles: no atomics); y = (x + 4) / 4.
+ *   basis: fp32 [400, 448] (the table of l2s_stft_mel_power), fb: fp32 [80, 201], fb_range: int32 [80, 2] - data of the caller;
+ *   out: 16-bit rows [B * 3000, ld] time-major, ld >= 80 a multiple of 8, columns 80 .. ld - 1 written as zeros (conv1's
+ *   tap-GEMM operand); out_f32: NULL or fp32 dense [B * 3000, 80], y before the rounding;
+ *   workspace: l2s_whisper_logmel_workspace(B) bytes, 16-byte aligned.  S > 480 000 returns L2S_EUNSUPPORTED (one 30-s window).
+ */
+size_t l2s_whisper_logmel_workspace(int B);
+int l2s_whisper_logmel(const void* wav, int wav_is_i16, int64_t ldw, const int32_t* n_samples, int B, int S, const float* basis,
+                       const float* fb, const int32_t* fb_range, void* workspace, void* out, int ld, float* out_f32, int dtype,
+                       void* stream);
+int l2s_kv_attention(const void* q, int ldq, void* k_cache, void* v_cache, int cache_T, const void* k_new, const void* v_new, int ld_new,
+                     const int32_t* pos, int pos_stride, int n_valid, int B, int H, void* out, int ldo, int dtype, void* stream);
+size_t l2s_vocab_argmax_workspace(int V, int B);
+int l2s_vocab_argmax(const void* x, int ldx, const void* emb, int lde, int B, int V, int d, const uint8_t* suppress,
+                     const uint8_t* begin_suppress, const int32_t* step, int first_step, void* workspace, int32_t* token, float* logprob,
+                     float* logits, int dtype, void* stream);
+int l2s_whisper_advance(int32_t* token, const float* logprob, int32_t* tokens, int ld_tok, float* sum_logprob, int32_t* lengths,
+                        uint8_t* done, const void* tok_emb, int lde, const float* pos_emb, int n_ctx, float* x_next, int ldx, int32_t* pos,
+                        int32_t* n_active, int B, int V, int d, int eot, int dtype, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -136,6 +136,12 @@ SIGNATURES = {
     "l2s_spk_embed_head": ([_vp, _i, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp], _i),
     "l2s_mouth_transforms": ([_vp, _i, _i, _vp, _vp, _i, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp], _i),
     "l2s_mouth_warp": ([_vp, _i, _i, _i, _i, _vp, _vp, _i, _i, _vp, _vp, _vp, _i, _f, _f, _vp], _i),
+    "l2s_whisper_logmel_workspace": ([_i], ctypes.c_size_t),
+    "l2s_whisper_logmel": ([_vp, _i, ctypes.c_int64, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _i, _vp, _i, _vp], _i),
+    "l2s_kv_attention": ([_vp, _i, _vp, _vp, _i, _vp, _vp, _i, _vp, _i, _i, _i, _i, _vp, _i, _i, _vp], _i),
+    "l2s_vocab_argmax_workspace": ([_i, _i], ctypes.c_size_t),
+    "l2s_vocab_argmax": ([_vp, _i, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _i, _vp], _i),
+    "l2s_whisper_advance": ([_vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _i, _vp, _i, _vp, _i, _vp, _vp, _i, _i, _i, _i, _i, _vp], _i),
 }
 
 _lib = None

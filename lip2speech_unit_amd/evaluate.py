@@ -106,13 +106,60 @@ def report(pairs, output_dir, batch_size=16, read=None, score=None, unpaired=Non
     return rep
 
 
+def read_transcripts(path, names):
+    """Reference texts of the clips `names` (relative *.wav names): a directory of <name>.txt files, or a tsv of `<name>\\t<text>`
+    lines (name with or without .wav).  Returns {name: text} for the names that have one."""
+    stem = lambda n: n[:-4] if n.endswith(".wav") else n  # noqa: E731
+    out = {}
+    if os.path.isdir(path):
+        for n in names:
+            f = os.path.join(path, stem(n) + ".txt")
+            if os.path.exists(f):
+                out[n] = open(f, encoding="utf-8").read().strip()
+        return out
+    table = {}
+    for line in open(path, encoding="utf-8"):
+        if line.strip():
+            k, _, t = line.rstrip("\n").partition("\t")
+            table[stem(k.strip())] = t.strip()
+    return {n: table[stem(n)] for n in names if stem(n) in table}
+
+
+def wer_report(items, transcripts, output_dir, transcribe):
+    """WER of the predicted clips against reference texts, the fourth number the reference publishes (README.md:103-122; formula
+    inference_server.py:364-373): items = [(name, pred_path)], transcribe(paths) -> texts.  Prints `WER xx.xx (n clips)`, writes
+    <output_dir>/eval-wer.json (wer, n_err, n_total and per clip name, ref, hyp, errors, words), returns the report."""
+    from .asr_text import wer
+    refs = read_transcripts(transcripts, [n for n, _ in items])
+    scored = [(n, pth) for n, pth in items if n in refs]
+    if not scored:
+        raise SystemExit(f"no clip has a transcript in {transcripts}")
+    hyps = transcribe([pth for _, pth in scored])
+    rep = wer([refs[n] for n, _ in scored], hyps)
+    for c, (n, _) in zip(rep["clips"], scored):
+        c["name"] = n
+    rep["no_transcript"] = [n for n, _ in items if n not in refs]
+    print("WER n/a (no reference words)" if rep["wer"] is None else f"WER {rep['wer']:.2f} ({len(scored)} clips, {rep['n_err']} / {rep['n_total']})")
+    os.makedirs(output_dir, exist_ok=True)
+    with open(os.path.join(output_dir, "eval-wer.json"), "w") as f:
+        json.dump(rep, f, indent=1)
+    return rep
+
+
 def main(argv=None, read=None, score=None):
     p = argparse.ArgumentParser()
     p.add_argument("ref_audio_dir")
     p.add_argument("pred_wav_dir")
     p.add_argument("--batch_size", type=int, default=16)
     p.add_argument("--output_dir", default="generated_files")
+    # --wer: also transcribe the predicted clips (whisper.WhisperASR) and score them against --transcripts; absent, nothing changes
+    p.add_argument("--wer", action="store_true", default=argparse.SUPPRESS)
+    p.add_argument("--transcripts", default=argparse.SUPPRESS, help="directory of <name>.txt files or a tsv of <name>\\t<text>")
+    from .transcribe import add_asr_arguments
+    add_asr_arguments(p, suppress=True)
     a = p.parse_args(argv)
+    if getattr(a, "wer", False) and not getattr(a, "transcripts", None):
+        p.error("--wer needs --transcripts (and --whisper, --vocab)")
     if score is None:
         import torch
         if not torch.cuda.is_available():
@@ -120,7 +167,14 @@ def main(argv=None, read=None, score=None):
     pairs, ref_only, pred_only = pair_files(a.ref_audio_dir, a.pred_wav_dir)
     if not pairs:
         raise SystemExit(f"no *.wav of {a.pred_wav_dir} has a partner of the same relative name below {a.ref_audio_dir}")
-    return report(pairs, a.output_dir, a.batch_size, read, score, {"ref_only": ref_only, "pred_only": pred_only})
+    rep = report(pairs, a.output_dir, a.batch_size, read, score, {"ref_only": ref_only, "pred_only": pred_only})
+    if getattr(a, "wer", False):
+        from . import transcribe
+        from .audio import read_wav_s16
+        asr = transcribe.asr_from_args(a)
+        wer_report([(n, pred) for n, _, pred in pairs], a.transcripts, a.output_dir,
+                   lambda paths: transcribe.transcribe_clips(asr, [read_wav_s16(pth) for pth in paths], getattr(a, "asr_batch_size", 16)))
+    return rep
 
 
 if __name__ == "__main__":

@@ -1070,6 +1070,150 @@ def mouth_warp(frames, inv, origin, *, crop_h=96, crop_w=96, roi=None, gray=None
         flops=14.0 * N * crop_h * crop_w * C, nbytes=float(out_bytes) + 4.0 * N * crop_h * crop_w * C, shape=f"N{N} {H}x{W}x{C}")
 
 
+def _req16(t, dtype, name):
+    _req(t, _TORCH16[dtype] if dtype in (F16, BF16) else None, name)
+    if dtype not in (F16, BF16):
+        raise L2SError(f"{name}: the decoder-step kernels take F16 or BF16 operands")
+
+
+WHISPER_SAMPLES, WHISPER_FRAMES, WHISPER_MELS = 480000, 3000, 80
+
+
+def whisper_logmel_workspace(B):
+    """Bytes of device workspace whisper_logmel needs (0 = unsupported B)."""
+    return int(_lib.load().l2s_whisper_logmel_workspace(B))
+
+
+def whisper_logmel(wav, workspace, out, basis, fb, fb_range, *, B, S, n_samples=None, ldw=None, ld=None, out_f32=None, dtype=F16):
+    """Whisper's log-mel input features (csrc/whisper_logmel.hip): wav fp32 or int16 [B, S <= 480 000] (zero-extended to 30 s),
+    n_samples int32 [B] real samples -> out 16-bit rows [B * 3000, ld] (80 bands, zeros in the columns past them) and, when given,
+    out_f32 fp32 [B * 3000, 80], the values before the rounding.  basis [400, 448] / fb [80, 201] / fb_range [80, 2]: whisper.LogMel's
+    tables.  workspace: whisper_logmel_workspace(B) bytes."""
+    ldw = ldw if ldw is not None else S
+    _wav_common("whisper_logmel", wav, n_samples, B, S, ldw)
+    _req16(out, dtype, "out")
+    ld = ld if ld is not None else out.stride(0)
+    _req(basis, torch.float32, "basis"), _req(fb, torch.float32, "fb"), _req(fb_range, torch.int32, "fb_range")
+    if basis.numel() < 400 * 448 or not basis.is_contiguous() or fb.numel() < 80 * 201 or not fb.is_contiguous() or fb_range.numel() < 160:
+        raise L2SError("whisper_logmel: tables smaller than [400, 448], [80, 201], [80, 2]")
+    if S > WHISPER_SAMPLES:
+        raise L2SError(f"whisper_logmel: a clip has at most {WHISPER_SAMPLES} samples (one 30-s window), got {S}")
+    if _extent(out) < (B * WHISPER_FRAMES - 1) * ld + ld:
+        raise L2SError("whisper_logmel: out smaller than [B * 3000, ld]")
+    if out_f32 is not None:
+        _req(out_f32, torch.float32, "out_f32")
+        if not out_f32.is_contiguous() or out_f32.numel() < B * WHISPER_FRAMES * WHISPER_MELS:
+            raise L2SError("whisper_logmel: out_f32 must be dense fp32 [B * 3000, 80]")
+    need = whisper_logmel_workspace(B)
+    if need == 0 or workspace.numel() * workspace.element_size() < need:
+        raise L2SError(f"whisper_logmel: workspace needs {need} bytes (0 = unsupported B)")
+    frames = float(B) * WHISPER_FRAMES
+    _run("l2s_whisper_logmel", lambda: _lib.load().l2s_whisper_logmel(
+        _ptr(wav), int(wav.dtype == torch.int16), ldw, _ptr(n_samples), B, S, _ptr(basis), _ptr(fb), _ptr(fb_range), _ptr(workspace),
+        _ptr(out), ld, _ptr(out_f32), dtype, _stream()),
+        flops=2.0 * frames * 400 * 448, nbytes=float(B) * S * wav.element_size() + frames * (8.0 * 80 + 2.0 * ld))
+
+
+def kv_attention(q, k_cache, v_cache, out, *, B, H, pos=None, pos_stride=0, n_valid=0, k_new=None, v_new=None, ldq=None, ld_new=None,
+                 ldo=None, dtype=F16):
+    """One query per (clip, head) against a key/value cache (csrc/whisper_decode.hip): q 16-bit [B, 64 H] (already scaled),
+    k_cache / v_cache 16-bit dense [B, cache_T, 64 H] -> out 16-bit [B, 64 H].  The valid length is pos[b * pos_stride] + 1 (pos:
+    device int32; pos_stride 0 = one position for the batch) or, without pos, n_valid.  k_new / v_new [B, 64 H] are stored at
+    cache row pos first (self-attention); rows at or past the valid length are never read."""
+    for t, n in ((q, "q"), (k_cache, "k_cache"), (v_cache, "v_cache"), (out, "out")):
+        _req16(t, dtype, n)
+    W = 64 * H
+    if k_cache.dim() != 3 or k_cache.shape != v_cache.shape or k_cache.shape[0] < B or k_cache.shape[2] != W \
+            or not k_cache.is_contiguous() or not v_cache.is_contiguous():
+        raise L2SError("kv_attention: k_cache / v_cache must be dense [B, cache_T, 64 H]")
+    cache_T = k_cache.shape[1]
+    if (k_new is None) != (v_new is None):
+        raise L2SError("kv_attention: k_new and v_new come together")
+    ldq = ldq if ldq is not None else q.stride(0)
+    ldo = ldo if ldo is not None else out.stride(0)
+    if k_new is not None:
+        _req16(k_new, dtype, "k_new"), _req16(v_new, dtype, "v_new")
+        ld_new = ld_new if ld_new is not None else k_new.stride(0)
+        if v_new.stride(0) != k_new.stride(0) or _extent(k_new) < (B - 1) * ld_new + W or _extent(v_new) < (B - 1) * ld_new + W:
+            raise L2SError("kv_attention: k_new / v_new must be [B, 64 H] with one row stride")
+    if pos is not None:
+        _req(pos, torch.int32, "pos")
+        if pos_stride not in (0, 1) or pos.numel() < 1 + (B - 1) * pos_stride:
+            raise L2SError("kv_attention: pos is one int32 (pos_stride 0) or [B] (pos_stride 1)")
+    if _extent(q) < (B - 1) * ldq + W or _extent(out) < (B - 1) * ldo + W:
+        raise L2SError("kv_attention: q / out smaller than [B, 64 H]")
+    _run("l2s_kv_attention", lambda: _lib.load().l2s_kv_attention(
+        _ptr(q), ldq, _ptr(k_cache), _ptr(v_cache), cache_T, _ptr(k_new), _ptr(v_new), ld_new or 0, _ptr(pos), pos_stride, n_valid,
+        B, H, _ptr(out), ldo, dtype, _stream()),
+        flops=4.0 * B * W * cache_T, nbytes=4.0 * B * W * cache_T, shape=f"B{B} H{H} T{cache_T}")
+
+
+def vocab_argmax_workspace(V, B):
+    """Bytes of device workspace vocab_argmax needs (0 = unsupported size)."""
+    return int(_lib.load().l2s_vocab_argmax_workspace(V, B))
+
+
+def vocab_argmax(x, emb, workspace, token, logprob, *, B, V, d, suppress=None, begin_suppress=None, step=None, first_step=0,
+                 logits=None, ldx=None, lde=None, dtype=F16):
+    """The tied output layer with the greedy choice fused in (csrc/whisper_decode.hip): x 16-bit [B, d], emb 16-bit [V, d] ->
+    token int32 [B] (argmax of x . emb^T over the ids neither uint8 mask forbids, ties to the smaller id), logprob fp32 [B] (its
+    log softmax over the allowed ids) and, when given, logits fp32 dense [B, V].  begin_suppress counts only when the device int32
+    step equals first_step.  workspace: vocab_argmax_workspace(V, B) bytes."""
+    _req16(x, dtype, "x"), _req16(emb, dtype, "emb")
+    _req(token, torch.int32, "token"), _req(logprob, torch.float32, "logprob")
+    ldx = ldx if ldx is not None else x.stride(0)
+    lde = lde if lde is not None else emb.stride(0)
+    if _extent(x) < (B - 1) * ldx + d or _extent(emb) < (V - 1) * lde + d or token.numel() < B or logprob.numel() < B:
+        raise L2SError("vocab_argmax: x [B, d], emb [V, d], token [B], logprob [B]")
+    for m, n in ((suppress, "suppress"), (begin_suppress, "begin_suppress")):
+        if m is not None:
+            _req(m, torch.uint8, n)
+            if m.numel() < V or not m.is_contiguous():
+                raise L2SError(f"vocab_argmax: {n} must be dense uint8 [V]")
+    if step is not None:
+        _req(step, torch.int32, "step")
+    if logits is not None:
+        _req(logits, torch.float32, "logits")
+        if not logits.is_contiguous() or logits.numel() < B * V:
+            raise L2SError("vocab_argmax: logits must be dense fp32 [B, V]")
+    need = vocab_argmax_workspace(V, B)
+    if need == 0 or workspace.numel() * workspace.element_size() < need:
+        raise L2SError(f"vocab_argmax: workspace needs {need} bytes (0 = unsupported V, B)")
+    _run("l2s_vocab_argmax", lambda: _lib.load().l2s_vocab_argmax(
+        _ptr(x), ldx, _ptr(emb), lde, B, V, d, _ptr(suppress), _ptr(begin_suppress), _ptr(step), first_step, _ptr(workspace),
+        _ptr(token), _ptr(logprob), _ptr(logits), dtype, _stream()),
+        flops=2.0 * B * V * d, nbytes=2.0 * V * d + 2.0 * B * d, shape=f"B{B} V{V} d{d}")
+
+
+def whisper_advance(token, logprob, tokens, sum_logprob, lengths, done, tok_emb, pos_emb, x_next, pos, n_active, *, B, V, d, eot,
+                    lde=None, ldx=None, dtype=F16):
+    """The bookkeeping of one decoder step (csrc/whisper_decode.hip), p = the device int32 pos: token int32 [B] (resolved in place:
+    eot once done), tokens int32 [B, max_steps] gets column p, sum_logprob fp32 [B] and lengths int32 [B] grow while a clip is not
+    done, done uint8 [B] is set on eot, x_next fp32 [B, d] = tok_emb[token] + pos_emb[p + 1]; then pos += 1 and n_active int32 [1]
+    = the clips not done."""
+    _req16(tok_emb, dtype, "tok_emb")
+    for t, dt, n, cnt in ((token, torch.int32, "token", B), (logprob, torch.float32, "logprob", B), (sum_logprob, torch.float32, "sum_logprob", B),
+                          (lengths, torch.int32, "lengths", B), (done, torch.uint8, "done", B), (pos, torch.int32, "pos", 1),
+                          (n_active, torch.int32, "n_active", 1)):
+        _req(t, dt, n)
+        if not t.is_contiguous() or t.numel() < cnt:
+            raise L2SError(f"whisper_advance: {n} must be dense with at least {cnt} elements")
+    _req(tokens, torch.int32, "tokens"), _req(pos_emb, torch.float32, "pos_emb"), _req(x_next, torch.float32, "x_next")
+    if tokens.dim() != 2 or not tokens.is_contiguous() or tokens.shape[0] < B:
+        raise L2SError("whisper_advance: tokens must be dense int32 [B, max_steps]")
+    ld_tok = tokens.shape[1]
+    lde = lde if lde is not None else tok_emb.stride(0)
+    ldx = ldx if ldx is not None else x_next.stride(0)
+    if pos_emb.dim() != 2 or pos_emb.shape[1] != d or not pos_emb.is_contiguous():
+        raise L2SError("whisper_advance: pos_emb must be dense fp32 [n_ctx, d]")
+    if _extent(tok_emb) < (V - 1) * lde + d or _extent(x_next) < (B - 1) * ldx + d:
+        raise L2SError("whisper_advance: tok_emb [V, d], x_next [B, d]")
+    _run("l2s_whisper_advance", lambda: _lib.load().l2s_whisper_advance(
+        _ptr(token), _ptr(logprob), _ptr(tokens), ld_tok, _ptr(sum_logprob), _ptr(lengths), _ptr(done), _ptr(tok_emb), lde,
+        _ptr(pos_emb), pos_emb.shape[0], _ptr(x_next), ldx, _ptr(pos), _ptr(n_active), B, V, d, eot, dtype, _stream()),
+        nbytes=10.0 * B * d)
+
+
 # ---- torch.library registration ("PyTorch-ROCm custom ops", SURVEY 8b last row) --------------------------------------------------
 # Every launcher above is ALSO a dispatcher-visible operator `torch.ops.lip2speech.<name>` (schema below, CUDA = HIP kernel only: a
 # CPU tensor finds no kernel and raises; a fake / meta implementation gives shapes to torch.compile and fake-tensor tracing), and
@@ -1196,6 +1340,17 @@ _SCHEMAS = {
                         "int start_idx=48, int stop_idx=68) -> ()",
     "mouth_warp": "(Tensor frames, Tensor inv, Tensor origin, *, int crop_h=96, int crop_w=96, Tensor(a!)? roi=None, "
                   "Tensor(b!)? gray=None, Tensor(c!)? model_in=None, int model_crop=88, float mean=0.421, float std=0.165) -> ()",
+    "whisper_logmel": "(Tensor wav, Tensor(a!) workspace, Tensor(b!) out, Tensor basis, Tensor fb, Tensor fb_range, *, int B, int S, "
+                      "Tensor? n_samples=None, int? ldw=None, int? ld=None, Tensor(c!)? out_f32=None, int dtype=0) -> ()",
+    "kv_attention": "(Tensor q, Tensor(a!) k_cache, Tensor(b!) v_cache, Tensor(c!) out, *, int B, int H, Tensor? pos=None, "
+                    "int pos_stride=0, int n_valid=0, Tensor? k_new=None, Tensor? v_new=None, int? ldq=None, int? ld_new=None, "
+                    "int? ldo=None, int dtype=0) -> ()",
+    "vocab_argmax": "(Tensor x, Tensor emb, Tensor(a!) workspace, Tensor(b!) token, Tensor(c!) logprob, *, int B, int V, int d, "
+                    "Tensor? suppress=None, Tensor? begin_suppress=None, Tensor? step=None, int first_step=0, "
+                    "Tensor(d!)? logits=None, int? ldx=None, int? lde=None, int dtype=0) -> ()",
+    "whisper_advance": "(Tensor(a!) token, Tensor logprob, Tensor(b!) tokens, Tensor(c!) sum_logprob, Tensor(d!) lengths, "
+                       "Tensor(e!) done, Tensor tok_emb, Tensor pos_emb, Tensor(f!) x_next, Tensor(g!) pos, Tensor(h!) n_active, *, "
+                       "int B, int V, int d, int eot, int? lde=None, int? ldx=None, int dtype=0) -> ()",
 }
 # C-ABI entry each operator launches (tests/test_torchlib_cpu.py: every device entry of include/lip2speech_hip.h has a twin)
 ENTRY_OF = {n: "l2s_" + n for n in _SCHEMAS}
@@ -1204,7 +1359,7 @@ ENTRY_OF.update({"maxpool2d_3x3s2": "l2s_maxpool2d_3x3s2", "avgpool_hw": "l2s_av
 HOST_QUERIES = ("l2s_abi_version", "l2s_build_info", "l2s_tapgemm_variant", "l2s_tapgemm_epilogue_family", "l2s_attention_variant", "l2s_layernorm_variant", "l2s_respair_variant",
                 "l2s_glu_dwconv_tile", "l2s_beam_decode_workspace",
                 "l2s_ctc_beam_workspace", "l2s_ctc_loss_workspace", "l2s_wave_stem_workspace", "l2s_kmeans_nearest_workspace",
-                "l2s_kmeans_update_workspace", "l2s_kmeans_pp_workspace")
+                "l2s_kmeans_update_workspace", "l2s_kmeans_pp_workspace", "l2s_vocab_argmax_workspace", "l2s_whisper_logmel_workspace")
 # SURVEY 8(b)'s operator names -> the entry that implements them (`mel_head` is a composition of linear_epilogue launches,
 # conformer.py::Conformer.forward_rows; it has no kernel of its own)
 ALIASES = {"frontend3d_stem": "stem_pool_fused", "resnet_trunk": "basiclayer_fused", "linear_epilogue": "tapgemm",

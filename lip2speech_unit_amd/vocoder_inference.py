@@ -63,6 +63,9 @@ def build_parser():
     p.add_argument("--stoi", action="store_true", default=argparse.SUPPRESS)   # absent: the namespace is what it was without the flag
     p.add_argument("--spk_emb_from_audio", action="store_true", default=argparse.SUPPRESS)   # absent likewise, and so is the next
     p.add_argument("--speaker_encoder", default=argparse.SUPPRESS)
+    p.add_argument("--asr", action="store_true", default=argparse.SUPPRESS)    # absent likewise, and so are the recogniser's options
+    from .transcribe import add_asr_arguments
+    add_asr_arguments(p, suppress=True)
     return p
 
 
@@ -130,6 +133,13 @@ def main(argv=None):
     if getattr(a, "stoi", False):
         from . import evaluate
         evaluate.report(written, a.output_dir)
+    if getattr(a, "asr", False):
+        from . import audio, transcribe
+        asr = transcribe.asr_from_args(a)
+        texts = transcribe.transcribe_clips(asr, [audio.read_wav_s16(out) for _, _, out in written], getattr(a, "asr_batch_size", 16))
+        transcribe.write_transcripts([name for name, _, _ in written], texts, a.output_dir)
+        for (name, _, _), t in zip(written, texts):
+            print(f"{name}\t{t}")
 
 
 if __name__ == "__main__":
