@@ -159,7 +159,9 @@ int l2s_stem_conv3d(const void* x, int x_is_f32, const void* w, const float* bia
  * after it, so NEGATIVE outputs are round16(s * round16(a)) instead of round16(s * a) - one 16-bit ulp at most from that;
  * the fused kernel also sums the taps in another order than l2s_stem_conv3d (different tiles), worth one more ulp on a small
  * share of the outputs of either sign (tests/test_kernels_gpu.py::test_stem_pool_fused_vs_two_step_launches: <= 2 ulp, < 2 %
- * of the outputs differ, both dtypes).
+ * of the outputs differ at T = 7, both dtypes).  The share follows the share of negative outputs - 4.2 % at T = 1 with that test's
+ * bias - and an output that has cancelled to less than the fp32 accumulation error of its 245 terms has no meaningful ulp: the two
+ * kernels then agree to that error, not to 2 ulp of the tiny value (profiles/frontend_matrix.md, Findings 1 and 2).
  */
 int l2s_stem_pool_fused(const void* x, int x_is_f32, const void* w, const float* bias, const float* slope,
                         void* y, int B, int T, int H, int W, int dtype, void* stream);
@@ -173,6 +175,11 @@ int l2s_stem_pool_fused(const void* x, int x_is_f32, const void* w, const float*
  */
 int l2s_stem_pool_fused_u8(const uint8_t* frames, int Hin, int Win, int crop, float mean, float std, const void* w,
                            const float* bias, const float* slope, void* y, int B, int T, int dtype, void* stream);
+/* l2s_stem_pool_frames (host-only: nothing is launched): the consecutive frames one block of the two fused stems above walks for
+ * B clips of T frames - 10, or 25 once 6 * ceil(T / 25) * B >= 2048 blocks remain, or L2S_STEM_FT of this process (any value
+ * >= 1: chunks shorter than the 5-frame window are fine, a block stages the whole window of its first frame); L2S_ESHAPE for
+ * B or T <= 0.  The chunking only decides which block computes a frame: results are bit-identical for every value. */
+int l2s_stem_pool_frames(int B, int T);
 
 /* MaxPool3d(k(1,3,3),s(1,2,2),p(0,1,1)) on channels-last frames, avhubert/resnet.py:141.  x:[N,H,W,C] -> y:[N,Ho,Wo,C] */
 int l2s_maxpool2d_3x3s2(const void* x, void* y, int N, int H, int W, int C, int dtype, void* stream);
@@ -406,6 +413,13 @@ int l2s_basicblock_fused(const void* x, const void* w1, const float* b1, const f
  */
 int l2s_basiclayer_fused(const void* x, const void* const* w, const float* const* bias, const float* const* slope, int n_blocks,
                          void* y, int n_images, int H, int W, int C, int dtype, void* stream);
+/* l2s_basicblock_variant (host-only, as l2s_respair_variant: nothing is launched, there is no pointer to dereference): which kernel
+ * l2s_basicblock_fused (n_blocks = 1) / l2s_basiclayer_fused run for these arguments under this process's L2S_BASICBLOCK_PHASE, or
+ * the error code a launch with valid, 16-byte aligned pointers gives.  The launchers ask the same function. */
+#define L2S_BB_PADDED64 576064  /* csrc/basicblock.hip: 576 padded positions per image, C = 64 */
+#define L2S_BB_PHASE64 512064   /* csrc/basicblock_phase.hip, CH = 64: 22 x 22, one image per 512-row tile */
+#define L2S_BB_PHASE128 256128  /* csrc/basicblock_phase.hip, CH = 128: 11 x 11, two images per 256-row tile */
+int l2s_basicblock_variant(int n_images, int H, int W, int C, int n_blocks, int dtype);
 /*
  * The rest of ResNet-18's strided 128-channel stage behind its first convolution, in one launch (avhubert/resnet.py:61-74 for a
  * block WITH downsample, :101-118 `_make_layer`, layer2 on the path: 22 x 22 x 64 -> 11 x 11 x 128):

@@ -15,6 +15,7 @@ F_RES_PRE, F_RES_POST, F_ACCUM, F_DUAL, F_MASK, F_OUT_F32, F_RES_F32 = (1 << i f
 MODE_LINEAR, MODE_CONV1D, MODE_CONV2D = 0, 1, 2
 ABI_VERSION = 16
 SEQ_VARIANT_F32, LN_GENERIC, ATTN_RESIDENT = 2000, 10, 1000   # l2s_layernorm_variant / l2s_attention_variant / l2s_glu_dwconv_tile
+BB_PADDED64, BB_PHASE64, BB_PHASE128 = 576064, 512064, 256128   # l2s_basicblock_variant
 
 _ERR = {-1: "L2S_EINVAL", -2: "L2S_ESHAPE", -3: "L2S_EALIGN", -4: "L2S_EUNSUPPORTED"}
 
@@ -101,6 +102,8 @@ SIGNATURES = {
     "l2s_lens_from_mask": ([_vp, _vp, _i, _i, _vp], _i),
     "l2s_basicblock_fused": ([_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp], _i),
     "l2s_basiclayer_fused": ([_vp, _vp, _vp, _vp, _i, _vp, _i, _i, _i, _i, _i, _vp], _i),
+    "l2s_basicblock_variant": ([_i, _i, _i, _i, _i, _i], _i),
+    "l2s_stem_pool_frames": ([_i, _i], _i),
     "l2s_basicstage128_tail_fused": ([_vp] * 12 + [_i, _i, _i, _i, _vp], _i),
     "l2s_split_hi_lo": ([_vp, _i, _vp, _vp, _i, _i, _f, _vp, _i, _i, _i, _i, _i, _vp], _i),
     "l2s_conv_post_tanh": ([_vp, _vp, _f, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp], _i),

@@ -346,28 +346,46 @@ int launch_bb(const BbArgs& a, hipStream_t st) {
 
 }  // namespace
 
-static int bb_launch_checked(const void* x, const void* const* w, const float* const* bias, const float* const* slope,
-                             int n_blocks, void* y, int n_images, int H, int W, int C, int dtype, void* stream) {
-  if (!x || !y || !w || !bias || !slope) return L2S_EINVAL;
+// Which kernel a launch with these arguments runs (the launch and l2s_basicblock_variant both ask here; pointers are the launch's
+// own business): L2S_BB_PADDED64 = this file's padded-position kernel, L2S_BB_PHASE64 / L2S_BB_PHASE128 = csrc/basicblock_phase.hip
+// at CH = 64 / 128, or the error code of the launch.
+static int bb_select(int n_images, int H, int W, int C, int n_blocks, int dtype) {
   if (n_images <= 0 || H <= 0 || W <= 0 || n_blocks <= 0) return L2S_ESHAPE;
   // A/B switch: L2S_BASICBLOCK_PHASE=0 keeps the 64-channel stage on this file's padded-position kernel
   static const bool phase64 = [] { const char* e = getenv("L2S_BASICBLOCK_PHASE"); return !(e && e[0] == '0'); }();
   if (C == 128 || (C == 64 && phase64 && l2s_basicblock_phase_supports(C, H, W) && n_blocks <= BB_MAXNB)) {
     // csrc/basicblock_phase.hip: the 128-channel stage (one block per launch) and layer1's 22 x 22 maps
     if ((C == 128 && n_blocks != 1) || !l2s_basicblock_phase_supports(C, H, W)) return L2S_EUNSUPPORTED;
-    if (((uintptr_t)x & 15) || ((uintptr_t)y & 15)) return L2S_EALIGN;
-    for (int j = 0; j < 2 * n_blocks; ++j) {
-      if (!w[j] || !bias[j] || !slope[j]) return L2S_EINVAL;
-      if (((uintptr_t)w[j] & 15) || ((uintptr_t)bias[j] & 15) || ((uintptr_t)slope[j] & 15)) return L2S_EALIGN;
-    }
     if ((int64_t)n_images * H * W * C >= ((int64_t)1 << 31)) return L2S_EUNSUPPORTED;
-    return l2s_basicblock_phase_launch(x, w, bias, slope, n_blocks, y, n_images, H, W, C, dtype, (hipStream_t)stream);
+    if (dtype != L2S_F16 && dtype != L2S_BF16) return L2S_EINVAL;
+    return C == 128 ? L2S_BB_PHASE128 : L2S_BB_PHASE64;
   }
   if (C != 64 || n_blocks > BB_MAXNB) return L2S_EUNSUPPORTED;
   // the block computes 576 padded positions; a tap reaches (W + 3) positions beyond the image on either side
   if ((H + 2) * (W + 2) > BB_NP || W + 3 > BB_HALO) return L2S_EUNSUPPORTED;
-  if (((uintptr_t)x & 15) || ((uintptr_t)y & 15)) return L2S_EALIGN;
   if ((int64_t)n_images * H * W * 64 >= ((int64_t)1 << 40)) return L2S_EUNSUPPORTED;
+  if (dtype != L2S_F16 && dtype != L2S_BF16) return L2S_EINVAL;
+  return L2S_BB_PADDED64;
+}
+
+/* include/lip2speech_hip.h: l2s_basicblock_variant */
+extern "C" int l2s_basicblock_variant(int n_images, int H, int W, int C, int n_blocks, int dtype) {
+  return bb_select(n_images, H, W, C, n_blocks, dtype);
+}
+
+static int bb_launch_checked(const void* x, const void* const* w, const float* const* bias, const float* const* slope,
+                             int n_blocks, void* y, int n_images, int H, int W, int C, int dtype, void* stream) {
+  if (!x || !y || !w || !bias || !slope) return L2S_EINVAL;
+  const int sel = bb_select(n_images, H, W, C, n_blocks, dtype);
+  if (sel < 0) return sel;
+  if (((uintptr_t)x & 15) || ((uintptr_t)y & 15)) return L2S_EALIGN;
+  if (sel != L2S_BB_PADDED64) {
+    for (int j = 0; j < 2 * n_blocks; ++j) {
+      if (!w[j] || !bias[j] || !slope[j]) return L2S_EINVAL;
+      if (((uintptr_t)w[j] & 15) || ((uintptr_t)bias[j] & 15) || ((uintptr_t)slope[j] & 15)) return L2S_EALIGN;
+    }
+    return l2s_basicblock_phase_launch(x, w, bias, slope, n_blocks, y, n_images, H, W, C, dtype, (hipStream_t)stream);
+  }
   BbArgs a;
   a.X = (const uint16_t*)x; a.Y = (uint16_t*)y;
   for (int i = 0; i < 2 * BB_MAXNB; ++i) {
@@ -378,8 +396,7 @@ static int bb_launch_checked(const void* x, const void* const* w, const float* c
   }
   a.nimg = n_images; a.H = H; a.W = W; a.nb = n_blocks;
   if (dtype == L2S_F16) return launch_bb<ElemF16>(a, (hipStream_t)stream);
-  if (dtype == L2S_BF16) return launch_bb<ElemBF16>(a, (hipStream_t)stream);
-  return L2S_EINVAL;
+  return launch_bb<ElemBF16>(a, (hipStream_t)stream);
 }
 
 extern "C" int l2s_basicblock_fused(const void* x, const void* w1, const float* b1, const float* s1, const void* w2,

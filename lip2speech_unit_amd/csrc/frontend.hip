@@ -593,6 +593,17 @@ static void launch_stem_pool(dim3 grid, hipStream_t st, const void* x, const uin
   else hipLaunchKernelGGL((stem_pool_kernel<ET, XK, true>), grid, dim3(256), 0, st, x, w, bias, slope, y, B, T, ft, u8);
 }
 
+// frames per block (stem_pool_dispatch and l2s_stem_pool_frames both ask here): every block pays the weight fetch, the LDS
+// initialisation and a five-slab window once; longer chunks amortise that as long as the grid still holds several rounds of the
+// 512 resident blocks
+static int stem_pool_frames(int B, int T) {
+  static const int ft_env = [] { const char* e = getenv("L2S_STEM_FT"); return e ? atoi(e) : 0; }();   // A/B switch
+  return ft_env > 0 ? ft_env : (6L * ((T + 24) / 25) * B >= 2048 ? 25 : FT);
+}
+
+/* include/lip2speech_hip.h: l2s_stem_pool_frames */
+extern "C" int l2s_stem_pool_frames(int B, int T) { return (B <= 0 || T <= 0) ? L2S_ESHAPE : stem_pool_frames(B, T); }
+
 static int stem_pool_dispatch(const void* x, int xk, const void* w, const float* bias, const float* slope, void* y, int B,
                               int T, int dtype, StemU8 u8, void* stream) {
   if (!x || !w || !bias || !y) return L2S_EINVAL;   // slope == NULL selects Swish (ESPnet Conv3dResNet) instead of PReLU
@@ -600,10 +611,7 @@ static int stem_pool_dispatch(const void* x, int xk, const void* w, const float*
   if (dtype == L2S_F32) return L2S_EUNSUPPORTED;    // fp32 runs l2s_stem_conv3d + l2s_maxpool2d_3x3s2
   if (((uintptr_t)w & 15) || ((uintptr_t)y & 15)) return L2S_EALIGN;
   if (xk != 2 && ((uintptr_t)x & 15)) return L2S_EALIGN;   // 16-bit / fp32 frames are fetched as 8- / 16-byte quads (uint8: any address)
-  // frames per block: every block pays the weight fetch, the LDS initialisation and a five-slab window once; longer chunks
-  // amortise that as long as the grid still holds several rounds of the 512 resident blocks
-  static const int ft_env = [] { const char* e = getenv("L2S_STEM_FT"); return e ? atoi(e) : 0; }();   // A/B switch
-  int ft = ft_env > 0 ? ft_env : (6L * ((T + 24) / 25) * B >= 2048 ? 25 : FT);
+  const int ft = stem_pool_frames(B, T);
   dim3 grid((22 + FP - 1) / FP, (T + ft - 1) / ft, B);
   hipStream_t st = (hipStream_t)stream;
   const uint16_t* wp = (const uint16_t*)w;

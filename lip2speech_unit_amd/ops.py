@@ -1357,7 +1357,7 @@ ENTRY_OF = {n: "l2s_" + n for n in _SCHEMAS}
 ENTRY_OF.update({"maxpool2d_3x3s2": "l2s_maxpool2d_3x3s2", "avgpool_hw": "l2s_avgpool_hw"})
 # host-side queries of the ABI (no launch, nothing for the dispatcher to see)
 HOST_QUERIES = ("l2s_abi_version", "l2s_build_info", "l2s_tapgemm_variant", "l2s_tapgemm_epilogue_family", "l2s_attention_variant", "l2s_layernorm_variant", "l2s_respair_variant",
-                "l2s_glu_dwconv_tile", "l2s_beam_decode_workspace",
+                "l2s_glu_dwconv_tile", "l2s_basicblock_variant", "l2s_stem_pool_frames", "l2s_beam_decode_workspace",
                 "l2s_ctc_beam_workspace", "l2s_ctc_loss_workspace", "l2s_wave_stem_workspace", "l2s_kmeans_nearest_workspace",
                 "l2s_kmeans_update_workspace", "l2s_kmeans_pp_workspace", "l2s_vocab_argmax_workspace", "l2s_whisper_logmel_workspace")
 # SURVEY 8(b)'s operator names -> the entry that implements them (`mel_head` is a composition of linear_epilogue launches,
