@@ -850,6 +850,66 @@ int l2s_whisper_advance(int32_t* token, const float* logprob, int32_t* tokens, i
                         uint8_t* done, const void* tok_emb, int lde, const float* pos_emb, int n_ctx, float* x_next, int ldx, int32_t* pos,
                         int32_t* n_active, int B, int V, int d, int eot, int dtype, void* stream);
 
+/*
+ * One beam-search step of the AV-HuBERT seq2seq lip reader (avhubert/hubert_asr.py:411-507, avhubert/decoder.py:38-243 and
+ * fairseq's sequence_generator.py as avhubert/infer_s2s.py drives it; the arithmetic is restated in DESIGN.md section 21).
+ * csrc/s2s_decode.hip holds the three entries.  As above, whatever changes from step to step is read from DEVICE memory: p = *step
+ * is the position (the index of the newest token of every live slot; 0 = the initial eos), and the double-buffered tables
+ * (tokens, anc, scores: leading dimension 2) are read at half p & 1 and written at half (p + 1) & 1.  No floating-point atomics,
+ * every reduction in a fixed order, a block reads one clip only: a clip's bytes do not depend on its batch mates or on the run.
+ * Row r = b * beam + slot everywhere.  n_live[b] is the number of live slots of clip b, finished[b] != 0 marks an inert clip.
+ *
+ * l2s_beam_attention - one query per (clip, beam slot, head), heads hd in {64, 128, 192} wide, W = H * hd:
+ *   q: 16-bit [B * beam, ldq], head h = columns hd h .. hd h + hd - 1, ALREADY scaled; out: 16-bit [B * beam, ldo].
+ *   Self form (k_new, v_new, anc, step given; enc_lens NULL): k_cache / v_cache 16-bit dense [B, beam, T, W] (T = L_max rows per
+ *   slot), k_new / v_new 16-bit [B * beam, ld_new]; slot i stores its new rows at (b, i, p) - nothing else of the caches is
+ *   written - and attends to keys t = 0 .. p: t < p from row (b, anc[p & 1][b, i, t], t), t = p from the new rows themselves.
+ *   anc: int16 [2, B, beam, T], kept by l2s_beam_advance.  The caches are never reordered.
+ *   Cross form (enc_lens given; k_new, v_new, anc NULL): k_cache / v_cache 16-bit dense [B, T, W] (T = T_enc), shared by the
+ *   clip's slots; keys t < min(max(enc_lens[b], 0), T).  Rows at or past the valid length are never read.
+ *   fp32 dot products, fp32 online softmax (v_exp_f32), 8 lane groups of a wave merged in a fixed order, one rounding to 16 bits.
+ *   A slot >= n_live[b] (n_live NULL: none), a slot of a finished clip (finished NULL: none) or, in the self form, a position
+ *   outside [0, T) writes zeros to out and nothing to the caches.  No valid key gives zeros.
+ *   Supported: W <= 1536, beam <= 64, T <= 32767, B <= 65535; ldq, ldo, ld_new multiples of 8, 16-bit pointers 16-byte aligned.
+ * l2s_beam_select - the 2 beam best continuations of a clip (sequence_generator.py:319-411 without prefix tokens or constraints):
+ *   logits: fp32 [B * beam, ldl], V columns used; scores: fp32 [2, B, beam], the slots' cumulative scores (taken as 0 at p = 0).
+ *   Per row, fp32: y = logits * (1 / temperature); lp = (y - max y) - log(sum exp(y - max y)); a NaN lp becomes -inf (a NaN logit
+ *   makes its whole row -inf, as torch's log_softmax does); lp[pad] = -inf; lp[unk] -= unk_penalty; p >= max_len[b] leaves only
+ *   eos finite; p < min_len makes eos -inf; s = lp + scores[p & 1][b, slot].  Slots considered: slot 0 alone at p = 0, else
+ *   slots < n_live[b] (NULL: beam).  Output, K = 2 beam per clip: cand_score fp32 / cand_slot / cand_token int32 [B, K], s
+ *   descending, a tie to the smaller flat index slot * V + token.  Radix select over the 64-bit keys (score bits, ~flat index) with
+ *   integer LDS histograms.  A finished clip's outputs are left as they are.  n_live[b] is clamped to [1, beam]: a clip that is
+ *   not finished always has a live slot (l2s_beam_advance sets n_live[b] = 0 only together with finished[b] = 1).
+ *   Supported: beam <= 64, 2 beam + 2 <= V <= 8192; l2s_beam_select_workspace(V, beam) returns 0 for an unsupported size (the
+ *   selection itself needs no global workspace).
+ * l2s_beam_advance - the bookkeeping of a step (sequence_generator.py:413-557, 605-745), a block per clip that is not finished:
+ *   walking the K candidates in order: token == eos: when its rank < beam, its score > -inf and the clip holds < beam hypotheses,
+ *   it is finalised as hypothesis number nhyp[b]++ : hyp_tokens[b, n, :] = tokens[p & 1][b, parent, 1 .. p], eos, then pad;
+ *   hyp_len = p + 1; hyp_score = score / (p + 1)^lenpen when normalize_scores, else score.  token != eos: the first `beam` such
+ *   candidates become slots j = 0, 1, ... of the other half: tokens and anc rows 0 .. p copied from the parent slot,
+ *   tokens[.., j, p + 1] = token, anc[.., j, p + 1] = j, scores[.., j] = score, parents[b, j] = parent slot,
+ *   x_next[b * beam + j, :d] = embed_scale * emb[token] + pos_table[p + 1] (fp32; emb 16-bit [V, lde], pos_table fp32 dense
+ *   [L, d], row t = the position embedding of token index t); n_live[b] = their count.
+ *   The clip is finished when nhyp[b] == beam or p >= max_len[b]: then finished[b] = 1, n_live[b] = 0, no new slots are
+ *   written and out_tokens / out_len / out_score [B, beam(, L)] receive the nhyp[b] hypotheses by score descending, ties in
+ *   finalisation order.  When p + 1 >= L nothing is written.  Last: *step = p + 1, *n_active = the clips not finished.
+ *   tokens: int32 [2, B, beam, L]; anc: int16 [2, B, beam, L]; hyp_* are the caller's work buffers.
+ *   Supported: beam <= 64, V <= 8192, d a multiple of 8 up to 1536, L <= 32767, B <= 65535.
+ */
+int l2s_beam_attention(const void* q, int ldq, void* k_cache, void* v_cache, int T, const void* k_new, const void* v_new, int ld_new,
+                       const int16_t* anc, const int32_t* step, const int32_t* enc_lens, const int32_t* n_live, const uint8_t* finished,
+                       int B, int beam, int H, int hd, void* out, int ldo, int dtype, void* stream);
+size_t l2s_beam_select_workspace(int V, int beam);
+int l2s_beam_select(const float* logits, int ldl, const float* scores, const int32_t* step, const int32_t* max_len, const int32_t* n_live,
+                    const uint8_t* finished, int B, int beam, int V, int pad, int unk, int eos, int min_len, float temperature,
+                    float unk_penalty, float* cand_score, int32_t* cand_slot, int32_t* cand_token, void* stream);
+int l2s_beam_advance(const float* cand_score, const int32_t* cand_slot, const int32_t* cand_token, int32_t* tokens, int16_t* anc,
+                     float* scores, int32_t* n_live, uint8_t* finished, int32_t* parents, int32_t* hyp_tokens, int32_t* hyp_len,
+                     float* hyp_score, int32_t* nhyp, int32_t* out_tokens, int32_t* out_len, float* out_score, const int32_t* max_len,
+                     const void* emb, int lde, const float* pos_table, float embed_scale, float* x_next, int ldx, int32_t* step,
+                     int32_t* n_active, int B, int beam, int L, int V, int d, int eos, int pad, float lenpen, int normalize_scores,
+                     int dtype, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

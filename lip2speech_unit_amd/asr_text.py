@@ -176,3 +176,56 @@ def wer(refs: Sequence[str], hyps: Sequence[str]) -> dict:
         n_err += e
         n_total += len(r.split())
     return {"wer": 100.0 * n_err / n_total if n_total else None, "n_err": n_err, "n_total": n_total, "clips": clips}
+
+
+class FairseqDictionary:
+    """fairseq's Dictionary as the lip reader's target side uses it (`dict.wrd.txt`: one `<symbol> <count>` line per sentencepiece
+    unit).  Ids 0 .. 3 are `<s> <pad> </s> <unk>` (nspecial = 4), the file's symbols follow in order.  `string` undoes the
+    sentencepiece segmentation the way fairseq's `post_process="sentencepiece"` does; no sentencepiece model is needed."""
+    BOS, PAD, EOS, UNK = 0, 1, 2, 3
+    SPECIALS = ("<s>", "<pad>", "</s>", "<unk>")
+
+    def __init__(self, symbols: Sequence[str] = ()):
+        self.symbols = list(self.SPECIALS)
+        self.nspecial = len(self.symbols)
+        self.symbols.extend(symbols)
+        self.index = {}
+        for i, s in enumerate(self.symbols):
+            self.index.setdefault(s, i)
+
+    @classmethod
+    def load(cls, path):
+        syms = []
+        with open(path, encoding="utf-8") as f:
+            for ln in f:
+                ln = ln.rstrip("\n")
+                if not ln:
+                    continue
+                if ln.endswith(" #fairseq:overwrite"):
+                    ln = ln[:-len(" #fairseq:overwrite")]
+                sym, _, cnt = ln.rpartition(" ")
+                if not sym or not cnt.lstrip("-").isdigit():
+                    raise ValueError(f"{path}: expected '<symbol> <count>', got {ln!r}")
+                syms.append(sym)
+        return cls(syms)
+
+    def __len__(self):
+        return len(self.symbols)
+
+    def pad(self):
+        return self.PAD
+
+    def eos(self):
+        return self.EOS
+
+    def unk(self):
+        return self.UNK
+
+    def encode_pieces(self, pieces: Sequence[str]) -> List[int]:
+        return [self.index.get(p, self.UNK) for p in pieces]
+
+    def string(self, ids: Sequence[int]) -> str:
+        """Text of a hypothesis: eos, pad and the initial bos dropped, `<unk>` kept as fairseq prints it, then
+        "".join(pieces).replace(" ", "").replace("▁", " ").strip()."""
+        pieces = [self.symbols[int(i)] for i in ids if int(i) not in (self.BOS, self.PAD, self.EOS)]
+        return " ".join(pieces).replace(" ", "").replace("▁", " ").strip()

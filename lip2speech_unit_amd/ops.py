@@ -1214,6 +1214,132 @@ def whisper_advance(token, logprob, tokens, sum_logprob, lengths, done, tok_emb,
         nbytes=10.0 * B * d)
 
 
+def _dense(t, dtype, name, count):
+    _req(t, dtype, name)
+    if not t.is_contiguous() or t.numel() < count:
+        raise L2SError(f"{name}: must be dense {dtype} with at least {count} elements")
+
+
+def beam_attention(q, k_cache, v_cache, out, *, B, beam, H, hd, k_new=None, v_new=None, anc=None, step=None, enc_lens=None,
+                   n_live=None, finished=None, ldq=None, ld_new=None, ldo=None, dtype=F16):
+    """One query per (clip, beam slot, head) (csrc/s2s_decode.hip): q / out 16-bit [B * beam, H hd], q already scaled.
+    Self form (k_new, v_new, anc int16 [2, B, beam, L], step int32 [1]): caches 16-bit dense [B, beam, L, H hd]; slot i stores its
+    new rows at (b, i, p) and reads position t < p from row (b, anc[p & 1][b, i, t], t).  Cross form (enc_lens int32 [B]): caches
+    dense [B, T_enc, H hd] shared by a clip's slots, keys t < enc_lens[b].  Slots >= n_live[b] and slots of a finished clip get zeros."""
+    for t, n in ((q, "q"), (k_cache, "k_cache"), (v_cache, "v_cache"), (out, "out")):
+        _req16(t, dtype, n)
+    W = H * hd
+    self_form = k_new is not None
+    if (k_new is None) != (v_new is None):
+        raise L2SError("beam_attention: k_new and v_new come together")
+    if self_form:
+        if anc is None or step is None or enc_lens is not None:
+            raise L2SError("beam_attention: the self form takes anc and step, and no enc_lens")
+        if k_cache.dim() != 4 or k_cache.shape != v_cache.shape or k_cache.shape[0] < B or k_cache.shape[1] != beam or k_cache.shape[3] != W \
+                or not k_cache.is_contiguous() or not v_cache.is_contiguous():
+            raise L2SError("beam_attention: self caches must be dense [B, beam, L, H hd]")
+        T = k_cache.shape[2]
+        _dense(anc, torch.int16, "anc", 2 * B * beam * T)
+        if anc.dim() != 4 or tuple(anc.shape) != (2, B, beam, T):
+            raise L2SError("beam_attention: anc must be int16 [2, B, beam, L] with the caches' B and L")
+        _dense(step, torch.int32, "step", 1)
+        _req16(k_new, dtype, "k_new"), _req16(v_new, dtype, "v_new")
+        ld_new = ld_new if ld_new is not None else k_new.stride(0)
+        need = (B * beam - 1) * ld_new + W
+        if v_new.stride(0) != k_new.stride(0) or _extent(k_new) < need or _extent(v_new) < need:
+            raise L2SError("beam_attention: k_new / v_new must be [B * beam, H hd] with one row stride")
+    else:
+        if enc_lens is None or anc is not None:
+            raise L2SError("beam_attention: the cross form takes enc_lens and no anc")
+        if k_cache.dim() != 3 or k_cache.shape != v_cache.shape or k_cache.shape[0] < B or k_cache.shape[2] != W \
+                or not k_cache.is_contiguous() or not v_cache.is_contiguous():
+            raise L2SError("beam_attention: cross caches must be dense [B, T_enc, H hd]")
+        T = k_cache.shape[1]
+        _dense(enc_lens, torch.int32, "enc_lens", B)
+    if n_live is not None:
+        _dense(n_live, torch.int32, "n_live", B)
+    if finished is not None:
+        _dense(finished, torch.uint8, "finished", B)
+    ldq = ldq if ldq is not None else q.stride(0)
+    ldo = ldo if ldo is not None else out.stride(0)
+    if _extent(q) < (B * beam - 1) * ldq + W or _extent(out) < (B * beam - 1) * ldo + W:
+        raise L2SError("beam_attention: q / out smaller than [B * beam, H hd]")
+    _run("l2s_beam_attention", lambda: _lib.load().l2s_beam_attention(
+        _ptr(q), ldq, _ptr(k_cache), _ptr(v_cache), T, _ptr(k_new), _ptr(v_new), ld_new or 0, _ptr(anc), _ptr(step), _ptr(enc_lens),
+        _ptr(n_live), _ptr(finished), B, beam, H, hd, _ptr(out), ldo, dtype, _stream()),
+        flops=4.0 * B * beam * W * T, nbytes=4.0 * B * (beam if self_form else 1) * W * T, shape=f"B{B} beam{beam} H{H} hd{hd} T{T}")
+
+
+def beam_select_workspace(V, beam):
+    """Nonzero when beam_select serves (V, beam): beam <= 64 and 2 beam + 2 <= V <= 8192 (the selection needs no global workspace)."""
+    return int(_lib.load().l2s_beam_select_workspace(V, beam))
+
+
+def beam_select(logits, scores, step, max_len, cand_score, cand_slot, cand_token, *, B, beam, V, pad, unk, eos, min_len=1,
+                temperature=1.0, unk_penalty=0.0, n_live=None, finished=None, ldl=None):
+    """The 2 beam best continuations of every clip (csrc/s2s_decode.hip): logits fp32 [B * beam, ldl] (V used), scores fp32
+    [2, B, beam] (half step & 1 is current) -> cand_score fp32 / cand_slot / cand_token int32 [B, 2 beam], score descending, a tie
+    to the smaller slot * V + token.  log_softmax(logits / temperature), NaN -> -inf, pad -inf, unk penalty, step >= max_len[b]
+    leaves eos only, step < min_len forbids eos; at step 0 only slot 0 counts, later the slots < n_live[b]."""
+    _req(logits, torch.float32, "logits")
+    ldl = ldl if ldl is not None else logits.stride(0)
+    if _extent(logits) < (B * beam - 1) * ldl + V:
+        raise L2SError("beam_select: logits smaller than [B * beam, V]")
+    if beam_select_workspace(V, beam) == 0:
+        raise L2SError(f"beam_select: unsupported size (beam {beam} <= 64, 2 beam + 2 <= V {V} <= 8192)")
+    K = 2 * beam
+    _dense(scores, torch.float32, "scores", 2 * B * beam), _dense(step, torch.int32, "step", 1), _dense(max_len, torch.int32, "max_len", B)
+    _dense(cand_score, torch.float32, "cand_score", B * K), _dense(cand_slot, torch.int32, "cand_slot", B * K)
+    _dense(cand_token, torch.int32, "cand_token", B * K)
+    if n_live is not None:
+        _dense(n_live, torch.int32, "n_live", B)
+    if finished is not None:
+        _dense(finished, torch.uint8, "finished", B)
+    _run("l2s_beam_select", lambda: _lib.load().l2s_beam_select(
+        _ptr(logits), ldl, _ptr(scores), _ptr(step), _ptr(max_len), _ptr(n_live), _ptr(finished), B, beam, V, pad, unk, eos, min_len,
+        float(temperature), float(unk_penalty), _ptr(cand_score), _ptr(cand_slot), _ptr(cand_token), _stream()),
+        nbytes=4.0 * B * beam * V * 5, shape=f"B{B} beam{beam} V{V}")
+
+
+def beam_advance(cand_score, cand_slot, cand_token, tokens, anc, scores, n_live, finished, parents, hyp_tokens, hyp_len, hyp_score,
+                 nhyp, out_tokens, out_len, out_score, max_len, emb, pos_table, x_next, step, n_active, *, B, beam, V, d, eos, pad,
+                 embed_scale=1.0, lenpen=1.0, normalize_scores=True, lde=None, ldx=None, dtype=F16):
+    """The bookkeeping of a beam step (csrc/s2s_decode.hip), p = the device int32 step: eos candidates among the first `beam` are
+    finalised into hyp_* (score / (p + 1)^lenpen when normalize_scores), the first `beam` other candidates become the slots of the
+    other half of tokens int32 / anc int16 [2, B, beam, L] / scores fp32 [2, B, beam] (parents int32 [B, beam]), x_next fp32
+    [B * beam, d] = embed_scale * emb[token] + pos_table[p + 1]; a clip finishes with `beam` hypotheses or at p >= max_len[b] and
+    then gets out_tokens / out_len / out_score sorted by score; last step += 1 and n_active = the clips not finished."""
+    _req16(emb, dtype, "emb")
+    if tokens.dim() != 4 or tokens.shape[0] != 2 or tokens.shape[1] != B or tokens.shape[2] != beam:
+        raise L2SError("beam_advance: tokens must be int32 [2, B, beam, L]")
+    L, K = tokens.shape[3], 2 * beam
+    _dense(tokens, torch.int32, "tokens", 2 * B * beam * L), _dense(anc, torch.int16, "anc", 2 * B * beam * L)
+    if tuple(anc.shape) != tuple(tokens.shape):
+        raise L2SError("beam_advance: anc must have tokens' shape")
+    for t, dt, n, cnt in ((cand_score, torch.float32, "cand_score", B * K), (cand_slot, torch.int32, "cand_slot", B * K),
+                          (cand_token, torch.int32, "cand_token", B * K), (scores, torch.float32, "scores", 2 * B * beam),
+                          (n_live, torch.int32, "n_live", B), (finished, torch.uint8, "finished", B),
+                          (parents, torch.int32, "parents", B * beam), (hyp_tokens, torch.int32, "hyp_tokens", B * beam * L),
+                          (hyp_len, torch.int32, "hyp_len", B * beam), (hyp_score, torch.float32, "hyp_score", B * beam),
+                          (nhyp, torch.int32, "nhyp", B), (out_tokens, torch.int32, "out_tokens", B * beam * L),
+                          (out_len, torch.int32, "out_len", B * beam), (out_score, torch.float32, "out_score", B * beam),
+                          (max_len, torch.int32, "max_len", B), (step, torch.int32, "step", 1), (n_active, torch.int32, "n_active", 1)):
+        _dense(t, dt, n, cnt)
+    _req(pos_table, torch.float32, "pos_table"), _req(x_next, torch.float32, "x_next")
+    if pos_table.dim() != 2 or pos_table.shape[0] < L or pos_table.shape[1] != d or not pos_table.is_contiguous():
+        raise L2SError("beam_advance: pos_table must be dense fp32 [>= L, d]")
+    lde = lde if lde is not None else emb.stride(0)
+    ldx = ldx if ldx is not None else x_next.stride(0)
+    if _extent(emb) < (V - 1) * lde + d or _extent(x_next) < (B * beam - 1) * ldx + d:
+        raise L2SError("beam_advance: emb [V, d], x_next [B * beam, d]")
+    _run("l2s_beam_advance", lambda: _lib.load().l2s_beam_advance(
+        _ptr(cand_score), _ptr(cand_slot), _ptr(cand_token), _ptr(tokens), _ptr(anc), _ptr(scores), _ptr(n_live), _ptr(finished),
+        _ptr(parents), _ptr(hyp_tokens), _ptr(hyp_len), _ptr(hyp_score), _ptr(nhyp), _ptr(out_tokens), _ptr(out_len), _ptr(out_score),
+        _ptr(max_len), _ptr(emb), lde, _ptr(pos_table), float(embed_scale), _ptr(x_next), ldx, _ptr(step), _ptr(n_active), B, beam, L, V,
+        d, eos, pad, float(lenpen), int(bool(normalize_scores)), dtype, _stream()),
+        nbytes=12.0 * B * beam * L + 6.0 * B * beam * d)
+
+
 # ---- torch.library registration ("PyTorch-ROCm custom ops", SURVEY 8b last row) --------------------------------------------------
 # Every launcher above is ALSO a dispatcher-visible operator `torch.ops.lip2speech.<name>` (schema below, CUDA = HIP kernel only: a
 # CPU tensor finds no kernel and raises; a fake / meta implementation gives shapes to torch.compile and fake-tensor tracing), and
@@ -1351,6 +1477,18 @@ _SCHEMAS = {
     "whisper_advance": "(Tensor(a!) token, Tensor logprob, Tensor(b!) tokens, Tensor(c!) sum_logprob, Tensor(d!) lengths, "
                        "Tensor(e!) done, Tensor tok_emb, Tensor pos_emb, Tensor(f!) x_next, Tensor(g!) pos, Tensor(h!) n_active, *, "
                        "int B, int V, int d, int eot, int? lde=None, int? ldx=None, int dtype=0) -> ()",
+    "beam_attention": "(Tensor q, Tensor(a!) k_cache, Tensor(b!) v_cache, Tensor(c!) out, *, int B, int beam, int H, int hd, "
+                      "Tensor? k_new=None, Tensor? v_new=None, Tensor? anc=None, Tensor? step=None, Tensor? enc_lens=None, "
+                      "Tensor? n_live=None, Tensor? finished=None, int? ldq=None, int? ld_new=None, int? ldo=None, int dtype=0) -> ()",
+    "beam_select": "(Tensor logits, Tensor scores, Tensor step, Tensor max_len, Tensor(a!) cand_score, Tensor(b!) cand_slot, "
+                   "Tensor(c!) cand_token, *, int B, int beam, int V, int pad, int unk, int eos, int min_len=1, float temperature=1.0, "
+                   "float unk_penalty=0.0, Tensor? n_live=None, Tensor? finished=None, int? ldl=None) -> ()",
+    "beam_advance": "(Tensor cand_score, Tensor cand_slot, Tensor cand_token, Tensor(a!) tokens, Tensor(b!) anc, Tensor(c!) scores, "
+                    "Tensor(d!) n_live, Tensor(e!) finished, Tensor(f!) parents, Tensor(g!) hyp_tokens, Tensor(h!) hyp_len, "
+                    "Tensor(i!) hyp_score, Tensor(j!) nhyp, Tensor(k!) out_tokens, Tensor(l!) out_len, Tensor(m!) out_score, "
+                    "Tensor max_len, Tensor emb, Tensor pos_table, Tensor(n!) x_next, Tensor(o!) step, Tensor(p!) n_active, *, int B, "
+                    "int beam, int V, int d, int eos, int pad, float embed_scale=1.0, float lenpen=1.0, bool normalize_scores=True, "
+                    "int? lde=None, int? ldx=None, int dtype=0) -> ()",
 }
 # C-ABI entry each operator launches (tests/test_torchlib_cpu.py: every device entry of include/lip2speech_hip.h has a twin)
 ENTRY_OF = {n: "l2s_" + n for n in _SCHEMAS}
@@ -1359,7 +1497,8 @@ ENTRY_OF.update({"maxpool2d_3x3s2": "l2s_maxpool2d_3x3s2", "avgpool_hw": "l2s_av
 HOST_QUERIES = ("l2s_abi_version", "l2s_build_info", "l2s_tapgemm_variant", "l2s_tapgemm_epilogue_family", "l2s_attention_variant", "l2s_layernorm_variant", "l2s_respair_variant",
                 "l2s_glu_dwconv_tile", "l2s_basicblock_variant", "l2s_stem_pool_frames", "l2s_beam_decode_workspace",
                 "l2s_ctc_beam_workspace", "l2s_ctc_loss_workspace", "l2s_wave_stem_workspace", "l2s_kmeans_nearest_workspace",
-                "l2s_kmeans_update_workspace", "l2s_kmeans_pp_workspace", "l2s_vocab_argmax_workspace", "l2s_whisper_logmel_workspace")
+                "l2s_kmeans_update_workspace", "l2s_kmeans_pp_workspace", "l2s_vocab_argmax_workspace", "l2s_whisper_logmel_workspace",
+                "l2s_beam_select_workspace")
 # SURVEY 8(b)'s operator names -> the entry that implements them (`mel_head` is a composition of linear_epilogue launches,
 # conformer.py::Conformer.forward_rows; it has no kernel of its own)
 ALIASES = {"frontend3d_stem": "stem_pool_fused", "resnet_trunk": "basiclayer_fused", "linear_epilogue": "tapgemm",
