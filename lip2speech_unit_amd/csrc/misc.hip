@@ -219,7 +219,7 @@ __global__ __launch_bounds__(256) void conv_post_kernel(const float* __restrict_
   for (int tap = 0; tap < k; ++tap) {
     const float* xr = sm + (threadIdx.x + tap) * ldc;
     const float* wr = sw + tap * C;
-    for (int c = 0; c < C; ++c) acc += xr[c] * wr[c];
+    for (int c = 0; c < C; ++c) acc = fmaf(xr[c], wr[c], acc);   // fused by name: conv_post16_kernel must round every term the same way
   }
   float o = tanhf(acc);
   if (t >= lim) o = 0.f;
@@ -255,14 +255,17 @@ __global__ __launch_bounds__(256) void conv_post16_kernel(const float* __restric
   __syncthreads();
   const int t = t0 + threadIdx.x;
   if (t >= T) return;
-  float acc = bias;                              // same summation order as the generic kernel: tap-major, channel-minor
+  // same summation order as the generic kernel (tap-major, channel-minor) and the same rounding: every term one fmaf, in both.
+  // Left to contraction, the compiler fused 100 of the 112 terms here and packed the last 12 into v_pk_mul_f32 + add: the two
+  // kernels then differed in the last bit of some samples of the same data (tests/test_glue_matrix_gpu.py, the (16, 7) twins).
+  float acc = bias;
 #pragma unroll
   for (int tap = 0; tap < K; ++tap) {
 #pragma unroll
     for (int q = 0; q < 4; ++q) {
       const float4 xv = *reinterpret_cast<const float4*>(sm + (threadIdx.x + tap) * LD + q * 4);
       const float4 wv = *reinterpret_cast<const float4*>(sw + tap * C + q * 4);
-      acc += xv.x * wv.x; acc += xv.y * wv.y; acc += xv.z * wv.z; acc += xv.w * wv.w;
+      acc = fmaf(xv.x, wv.x, acc); acc = fmaf(xv.y, wv.y, acc); acc = fmaf(xv.z, wv.z, acc); acc = fmaf(xv.w, wv.w, acc);
     }
   }
   float o = tanhf(acc);

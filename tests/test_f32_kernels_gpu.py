@@ -1,4 +1,5 @@
 """The fp32 (ops.F32) kernels against fp64 references computed on the CPU.
+rows_f32_kernel (l2s_f32_rows) has its matrix, on guarded buffers, in tests/test_glue_matrix_gpu.py.
 
 Tap-GEMM (csrc/tapgemm_f32.hip).  Every output is a k-ordered fp32 fma chain (one rounding per product) followed by the
 epilogue's few operations, so the bound is the chain's worst case, not a tolerance:

@@ -1,4 +1,5 @@
-"""Non-GEMM kernels of the C ABI vs the torch-fp32 CPU computation they replace."""
+"""Non-GEMM kernels of the C ABI vs the torch-fp32 CPU computation they replace.
+The unit decoders and the layout / cast kernels have their fp64 matrix in tests/test_glue_matrix_gpu.py."""
 import math
 import os
 

@@ -1,6 +1,7 @@
 """Text supervision on the MI355X: l2s_ctc_frames against torch fp32 softmax, l2s_ctc_beam_search against the CPU
 restatement of ctcdecode (tests/_ctc_reference.py), the conformer's text head against the oracle conformer output, graph
-capture, and the stage-1 CLI's pred_text files."""
+capture, and the stage-1 CLI's pred_text files.
+The edges of l2s_ctc_frames and l2s_ctc_repeat_labels are in the matrix of tests/test_glue_matrix_gpu.py."""
 import os
 
 import numpy as np
