@@ -910,6 +910,30 @@ int l2s_beam_advance(const float* cand_score, const int32_t* cand_slot, const in
                      int32_t* n_active, int B, int beam, int L, int V, int d, int eos, int pad, float lenpen, int normalize_scores,
                      int dtype, void* stream);
 
+/*
+ * Log filterbank features of 16 kHz waveforms, as rows for AV-HuBERT's audio sub-model (csrc/logfbank.hip): in one launch the
+ * python_speech_features.logfbank(wav, samplerate=16000) recipe at that library's defaults followed by the stacker, the alignment
+ * to the video's frame count and the F.layer_norm of avhubert/hubert_dataset.py:299-315,370-372, restated in fp32.
+ *   wav: int16 or fp32 [B, S] with row stride ldw, samples at INT16 SCALE either way (fp32 input is not rescaled);
+ *   n_samples: int32 [B] clip lengths or NULL (all S); lengths above S are taken as S, lengths <= 0 give zero rows.
+ * Per clip: y[0] = x[0], y[p] = x[p] - rn(0.97 x[p-1]) over the whole clip; frames of 400 samples every 160, zeros past the clip's
+ * end, n_frames = 1 if n <= 400 else 1 + ceil((n - 400) / 160), no window; pspec[k] = fma(im, im, rn(re re)) / 512 of the 512-point
+ * DFT, bins 0 .. 255; e[j] = sum_k fb[j][k] pspec[k] (k ascending over fb_range[j]); feat[j] = logf(e[j]), and the constant
+ * float(log(2.220446049250313e-16)) for a sum that is exactly 0.  `stack` consecutive frames form one row of 26 stack columns; the frames the last row lacks
+ * are 0.0 (padded after the log).  Clip b's rows at or past min(ceil(n_frames / stack), n_rows[b]) - to the end of its T_rows - are
+ * written as zeros; n_rows NULL = the audio's own row count.  With normalize != 0 every row is (x - mean) / sqrt(var + 1e-5) with the
+ * biased variance, two passes in fp32, the mean taken about the row's first value; an all-zero row stays zero, a constant row becomes zero.  Every clip is analysed alone.
+ *   basis: fp32 [400][512], 16-byte aligned, row n = sample of the frame, column c: tile q = c / 32, lane l = c % 32, bin
+ *     k = 32 (q / 2) + l; even q holds cos(2 pi k n / 512), odd q -sin(2 pi k n / 512).  Bin 256 has weight 0 in every band and no column.
+ *   fb: fp32 [26][257] dense filterbank; fb_range: int32 [26][2] = [first, past-last) bin of each band's non-zero weights.
+ *   out: fp32 (out_dtype L2S_F32) or 16-bit (L2S_F16 / L2S_BF16) [B, T_rows, 26 stack] with row stride ldo >= 26 stack; columns
+ *     past 26 stack are not written.
+ * Supported: stack 1 and 4; other values return L2S_EUNSUPPORTED.  B <= 65535, S < 2^30, T_rows stack <= 2^22.
+ */
+int l2s_logfbank(const void* wav, int wav_is_i16, int64_t ldw, const int32_t* n_samples, int B, int S, const float* basis,
+                 const float* fb, const int32_t* fb_range, const int32_t* n_rows, void* out, int out_dtype, int ldo, int T_rows,
+                 int stack, int normalize, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

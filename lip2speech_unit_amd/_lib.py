@@ -149,6 +149,7 @@ SIGNATURES = {
     "l2s_beam_select_workspace": ([_i, _i], ctypes.c_size_t),
     "l2s_beam_select": ([_vp, _i, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _f, _f, _vp, _vp, _vp, _vp], _i),
     "l2s_beam_advance": ([_vp] * 17 + [_vp, _i, _vp, _f, _vp, _i, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _f, _i, _i, _vp], _i),
+    "l2s_logfbank": ([_vp, _i, ctypes.c_int64, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp], _i),
 }
 
 _lib = None

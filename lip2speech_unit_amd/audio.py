@@ -208,6 +208,92 @@ class MelSpectrogram(_DeviceTables):
         return self.mel_rows(y).transpose(1, 2)
 
 
+def logfbank_filterbank(nfilt=26, nfft=512, sr=16000):
+    """python_speech_features.get_filterbanks at its defaults: triangular filters between the bin edges
+    floor((nfft + 1) mel2hz(linspace(0, hz2mel(sr / 2), nfilt + 2)) / sr), hz2mel(f) = 2595 log10(1 + f / 700); float64
+    [nfilt, nfft / 2 + 1].  The last edge is nfft / 2 exactly, so bin nfft / 2 has weight 0 in every filter."""
+    mel = np.linspace(0.0, 2595.0 * np.log10(1.0 + (sr / 2.0) / 700.0), nfilt + 2)
+    edges = np.floor((nfft + 1) * (700.0 * (10.0 ** (mel / 2595.0) - 1.0)) / sr).astype(np.int64)
+    fb = np.zeros((nfilt, nfft // 2 + 1))
+    for j in range(nfilt):
+        lo, mid, hi = int(edges[j]), int(edges[j + 1]), int(edges[j + 2])
+        i = np.arange(lo, mid)
+        fb[j, i] = (i - lo) / (mid - lo)
+        i = np.arange(mid, hi)
+        fb[j, i] = (hi - i) / (hi - mid)
+    return fb, edges
+
+
+def logfbank_frames(n, frame=400, hop=160):
+    """Frames python_speech_features.framesig makes of n samples: 1 if n <= frame, else 1 + ceil((n - frame) / hop)."""
+    n = int(n)
+    return 1 if n <= frame else 1 + -((frame - n) // hop)
+
+
+def logfbank_rows(n, stack=4):
+    """Rows of the stacker (hubert_dataset.py:299-304): ceil(frames / stack)."""
+    return -(-logfbank_frames(n) // int(stack))
+
+
+class LogFbank(_DeviceTables):
+    """The audio features of AV-HuBERT (hubert_dataset.py:299-315,370-372) on the device: python_speech_features.logfbank at 16 kHz
+    with that library's defaults (pre-emphasis 0.97, 400-sample frames every 160, no window, 512-point power spectrum / 512, 26
+    triangular filters, log with a zero energy taken as float eps), `stack` frames per row, rows padded or trimmed to the video's
+    frame count, and the per-row layer norm.  Tables are float64, rounded to float32 once, uploaded once per device (the basis is
+    [400, 512] in the column order of csrc/frame_dft.h).  There is no CPU path."""
+    N_FRAME, HOP, N_DFT, NFILT = 400, 160, 512, 26
+
+    def __init__(self, stack=4, normalize=True):
+        if stack not in (1, 4):
+            raise ValueError(f"stack_order_audio = {stack}: 1 and 4 are built")
+        self.stack, self.normalize = int(stack), bool(normalize)
+        k, part = packed_bins(np.arange(self.N_DFT))
+        self.basis = dft_basis(self.N_FRAME, self.N_DFT, k, part, np.ones(self.N_FRAME)).astype(np.float32)
+        fb, self.edges = logfbank_filterbank(self.NFILT, self.N_DFT)
+        self.fb = fb.astype(np.float32)
+        self.fb_range = band_ranges(self.fb)
+        self._dev = {}
+
+    @property
+    def width(self):
+        return self.NFILT * self.stack
+
+    def rows(self, wav, n_samples=None, n_rows=None, T_rows=None, out=None, dtype=torch.float32):
+        """wav: device tensor [B, S], int16 PCM or float AT INT16 SCALE.  n_samples: clip lengths - None (all S), a host sequence
+        (checked: 0 < n <= S) or an int32 device tensor (not read on the host).  n_rows: the video's frame counts in the same
+        forms, or None for the audio's own row counts.  Returns `out`, [B, T_rows, 26 * stack] of `dtype` (default T_rows: the
+        largest n_rows when it is a host sequence, else logfbank_rows(S)); clip b's rows past min(its rows, n_rows[b]) are zeros."""
+        if not isinstance(wav, torch.Tensor) or not wav.is_cuda:
+            raise L2SError("LogFbank.rows: expected a device tensor (there is no CPU path)")
+        if wav.dim() != 2:
+            raise ValueError("wav: [B, S]")
+        B, S = wav.shape
+        if wav.stride(1) != 1:
+            wav = wav.contiguous()
+
+        def lengths(v, name, hi):
+            if v is None or (isinstance(v, torch.Tensor) and v.is_cuda):
+                if v is not None and (v.dtype != torch.int32 or v.shape != (B,)):
+                    raise ValueError(f"{name}: int32 [B]")
+                return v if v is None else v.contiguous(), None
+            host = [int(x) for x in (v.tolist() if hasattr(v, "tolist") else v)]
+            if len(host) != B:
+                raise ValueError(f"{name}: one value per clip")
+            if any(x <= 0 or (hi is not None and x > hi) for x in host):
+                raise ValueError(f"{name}: every clip needs 0 < n" + (f" <= {hi}" if hi is not None else "") + f", got {host}")
+            return torch.tensor(host, dtype=torch.int32).to(wav.device), host
+        n_samples, _ = lengths(n_samples, "n_samples", S)
+        n_rows, host_rows = lengths(n_rows, "n_rows", None)
+        if T_rows is None:
+            T_rows = out.shape[1] if out is not None else (max(host_rows) if host_rows else logfbank_rows(S, self.stack))
+        if out is None:
+            out = torch.empty(B, T_rows, self.width, device=wav.device, dtype=dtype)
+        basis, fb, fb_range = self.tables(wav.device)
+        ops.logfbank(wav, out, basis, fb, fb_range, B=B, S=S, T_rows=T_rows, stack=self.stack, normalize=self.normalize,
+                     n_samples=n_samples, n_rows=n_rows, ldw=wav.stride(0) if B > 1 else S, ldo=out.stride(-2))
+        return out
+
+
 _default = None
 
 

@@ -245,7 +245,8 @@ class SubModel(nn.Module):
 
 
 class AVHubertModel(nn.Module, PackedState):
-    """Inference subset of avhubert/hubert.py:334-440: video-only extract_finetune."""
+    """Inference subset of avhubert/hubert.py:334-440: the video-only extract_finetune, and the two-stream fusion of :703-727
+    (audio rows and / or video, 'concat' or 'add') as extract_av_rows."""
 
     def __init__(self, cfg: AVHubertConfig = None, dtype=ops.F16):
         super().__init__()
@@ -255,9 +256,11 @@ class AVHubertModel(nn.Module, PackedState):
         resnet = ResEncoder(relu_type=cfg.resnet_relu_type, weights=None, dtype=dtype)
         self.feature_extractor_audio = SubModel(resnet=None, input_dim=cfg.audio_feat_dim, cfg=cfg)
         self.feature_extractor_video = SubModel(resnet=resnet, input_dim=resnet.backend_out, cfg=cfg)
-        if cfg.modality_fuse != "concat":
-            raise NotImplementedError("modality_fuse='add' is not used by the lip2speech checkpoints")
-        self.embed = 2 * d
+        if cfg.modality_fuse not in ("concat", "add"):
+            raise NotImplementedError(f"modality_fuse={cfg.modality_fuse!r}: 'concat' and 'add' are built")
+        if cfg.audio_feat_dim % 8:
+            raise NotImplementedError("audio_feat_dim must be a multiple of 8 (the audio projection is one tap-GEMM)")
+        self.embed = 2 * d if cfg.modality_fuse == "concat" else d
         self.encoder_embed_dim = d
         self.post_extract_proj = nn.Linear(self.embed, d)
         self.mask_emb = nn.Parameter(torch.zeros(cfg.audio_feat_dim))  # kept for checkpoint key parity (unused)
@@ -268,10 +271,12 @@ class AVHubertModel(nn.Module, PackedState):
 
     def pack(self, dev):
         t16 = ops.torch_dtype(self.dtype)
-        fv = self.feature_extractor_video
+        fv, fa = self.feature_extractor_video, self.feature_extractor_audio
         self._set_packed(dev, {
             "wp": fv.proj.weight.detach().to(dev, t16).contiguous(),
             "bp": fv.proj.bias.detach().float().to(dev).contiguous(),
+            "wa": fa.proj.weight.detach().to(dev, t16).contiguous(),
+            "ba": fa.proj.bias.detach().float().to(dev).contiguous(),
             "ln": (self.layer_norm.weight.detach().float().to(dev).contiguous(),
                    self.layer_norm.bias.detach().float().to(dev).contiguous()),
             "wpe": self.post_extract_proj.weight.detach().to(dev, t16).contiguous(),
@@ -292,6 +297,8 @@ class AVHubertModel(nn.Module, PackedState):
 
     def extract_rows(self, video, padding_mask):
         """Hot path: video [B,1,T,88,88], padding_mask [B,T] bool or None -> (fp32 [B*T, d] rows (b,t), lens int32 [B])."""
+        if self.cfg.modality_fuse != "concat":
+            return self.extract_av_rows(video=video, padding_mask=padding_mask)
         dev = video.device
         P, dt = self.packed(dev), self.dtype
         t16 = ops.torch_dtype(dt)
@@ -308,6 +315,53 @@ class AVHubertModel(nn.Module, PackedState):
         # post_extract_proj :727; rows of padded frames are zeroed here (TransformerEncoder: x[padding_mask] = 0)
         ops.tapgemm(fused, P["wpe"], x32, M=M, N=d, Cin=2 * d, bias=P["bpe"], C2=x16, ldc2=d, lens=lens, mask_T=T,
                     mask_mul=1, flags=F_MASK | F_DUAL, slope2=1.0, dtype=dt)
+        out = self.encoder.forward_rows(x32, x16, lens, B, T)                         # :739
+        return out, lens, B, T
+
+    def extract_av_rows(self, audio=None, video=None, padding_mask=None):
+        """The two-stream extract_finetune (hubert.py:703-745): audio [B, T, audio_feat_dim] rows in the model's 16-bit type
+        (audio.LogFbank makes them, aligned to the video's frames) and / or video [B,1,T,88,88] -> what extract_rows returns.
+        'concat': the two projections write the left (audio) and right (video) halves of one fp32 [M, 2 d] buffer, an absent
+        stream's half is zeros (:703-708); 'add': the second projection accumulates onto the first through the residual
+        epilogue.  Then layer_norm over the fused width and post_extract_proj.  Video alone with 'concat' is extract_rows."""
+        if audio is None and video is None:
+            raise ValueError("extract_av_rows needs audio rows, video, or both")
+        concat = self.cfg.modality_fuse == "concat"
+        if audio is None and concat:
+            return self.extract_rows(video, padding_mask)
+        dev = (audio if audio is not None else video).device
+        P, dt = self.packed(dev), self.dtype
+        t16 = ops.torch_dtype(dt)
+        d, E, Fa = self.encoder_embed_dim, self.embed, self.cfg.audio_feat_dim
+        if video is not None:
+            feat, B, T = self.feature_extractor_video.resnet.forward_rows(video)     # hubert.py:707 -> :324-326
+        if audio is not None:
+            if audio.dim() != 3 or audio.shape[2] != Fa or audio.dtype != t16 or not audio.is_contiguous():
+                raise ValueError(f"audio: contiguous {t16} rows [B, T, {Fa}]")
+            if video is not None and tuple(audio.shape[:2]) != (B, T):
+                raise ValueError(f"audio rows {tuple(audio.shape[:2])} do not match the video's (B, T) = {(B, T)}")
+            B, T = audio.shape[:2]
+        M = B * T
+        lens = self.lens_from_padding_mask(padding_mask, B, T, dev)
+        feats = torch.empty(M, E, device=dev, dtype=torch.float32)
+        if audio is not None:                                                        # :704 / :710 -> :327, the left half
+            ops.tapgemm(audio, P["wa"], feats, M=M, N=d, Cin=Fa, ldc=E, bias=P["ba"], dtype=dt)
+        elif concat:
+            feats[:, :d].zero_()
+        if video is not None:                                                        # the right half, or onto the audio rows
+            cv = feats[:, d:] if concat else feats
+            if audio is not None and not concat:
+                ops.tapgemm(feat, P["wp"], cv, M=M, N=d, Cin=feat.shape[1], ldc=E, bias=P["bp"], R=cv, ldr=E, flags=F_RES_POST, dtype=dt)
+            else:
+                ops.tapgemm(feat, P["wp"], cv, M=M, N=d, Cin=feat.shape[1], ldc=E, bias=P["bp"], dtype=dt)
+        elif concat:
+            feats[:, d:].zero_()                                                     # :705
+        fused = torch.empty(M, E, device=dev, dtype=t16)
+        ops.layernorm(feats, P["ln"][0], P["ln"][1], 1e-5, fused, M=M, C=E, dtype=dt)   # :712-720
+        x32 = torch.empty(M, d, device=dev, dtype=torch.float32)
+        x16 = torch.empty(M, d, device=dev, dtype=t16)
+        ops.tapgemm(fused, P["wpe"], x32, M=M, N=d, Cin=E, bias=P["bpe"], C2=x16, ldc2=d, lens=lens, mask_T=T,
+                    mask_mul=1, flags=F_MASK | F_DUAL, slope2=1.0, dtype=dt)         # :727, padded rows zeroed
         out = self.encoder.forward_rows(x32, x16, lens, B, T)                         # :739
         return out, lens, B, T
 

@@ -34,7 +34,8 @@ DEFAULTS = {
 }
 
 
-def parse_overrides(argv):
+def read_overrides(argv):
+    """DEFAULTS updated by the `key=value` arguments; what the values mean is the caller's check."""
     cfg = dict(DEFAULTS)
     for a in argv:
         if a.startswith("--") or "=" not in a:
@@ -44,9 +45,18 @@ def parse_overrides(argv):
         if k not in DEFAULTS:
             raise SystemExit(f"unknown override '{k}' (known: {', '.join(sorted(DEFAULTS))})")
         cfg[k] = s1._scalar(v)
+    return cfg
+
+
+def modality_names(mods):
+    return [m.strip(" '\"") for m in str(mods).strip("[]").split(",") if m.strip(" '\"")]
+
+
+def parse_overrides(argv):
+    cfg = read_overrides(argv)
     mods = cfg["override.modalities"]
     if mods is not None:
-        names = [m.strip(" '\"") for m in str(mods).strip("[]").split(",") if m.strip(" '\"")]
+        names = modality_names(mods)
         if names != ["video"]:
             raise SystemExit(f"override.modalities={mods}: the lip reader takes video only")
         cfg["override.modalities"] = names
@@ -63,8 +73,9 @@ def search_config(cfg):
                             normalize_scores=not bool(g("unnormalized")), nbest=int(g("nbest")))
 
 
-def read_manifest(label_dir, subset):
-    """(root, [(fid, video path, n_frames)], references or None)."""
+def read_manifest(label_dir, subset, audio=False):
+    """(root, [(fid, video path, n_frames)], references or None); audio=True: the clips also carry the tsv's audio column and
+    sample count, (fid, video path, n_frames, audio path, n_samples)."""
     with open(os.path.join(label_dir, subset + ".tsv")) as f:
         root = f.readline().strip()
         rows = [ln.rstrip("\n").split("\t") for ln in f if ln.strip()]
@@ -74,6 +85,10 @@ def read_manifest(label_dir, subset):
         refs = open(p, encoding="utf-8").read().splitlines()
         if len(refs) != len(rows):
             raise SystemExit(f"{p} has {len(refs)} lines for {len(rows)} clips")
+    if audio:
+        if any(len(r) < 5 for r in rows):
+            raise SystemExit(f"{label_dir}/{subset}.tsv: id, video path, audio path, frame count, sample count expected")
+        return root, [(r[0], r[1], int(r[-2]), r[2], int(r[-1])) for r in rows], refs
     return root, [(r[0], r[1], int(r[-2])) for r in rows], refs
 
 
@@ -117,6 +132,12 @@ def main(argv=None):
         for i, text in zip(idx, reader.transcribe(video, mask)):
             hyps[i] = text
             logger.info("HYP (%s): %s", clips[i][0], text)
+    return write_results(cfg, clips, refs, hyps, logger)
+
+
+def write_results(cfg, clips, refs, hyps, logger):
+    """hypo-<fid>.json and, with references, wer.<fid> under common_eval.results_path; returns what the json holds (and the WER)."""
+    results_path = cfg["common_eval.results_path"]
     fid = cfg["fid"] if cfg["fid"] is not None else os.getpid()
     out = {"utt_id": [c[0] for c in clips], "ref": refs if refs is not None else [""] * len(clips), "hypo": hyps}
     with open(os.path.join(results_path, f"hypo-{fid}.json"), "w") as f:

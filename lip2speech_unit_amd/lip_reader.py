@@ -321,17 +321,17 @@ class AVHubertSeq2Seq(nn.Module, PackedState):
         return self.encoder.w2v_model.extract_rows(video, padding_mask)
 
 
-def load_lip_reader(path, dtype=ops.F16):
-    """A fine-tuned AV-HuBERT seq2seq checkpoint (fairseq layout: `cfg.model` or old-style `args`, `model`) -> AVHubertSeq2Seq in
-    eval mode.  The encoder is sized from the pre-training config the checkpoint embeds (`w2v_args`), the decoder from the
-    fine-tuning fields, the vocabulary from `decoder.embed_tokens.weight`.  Sinusoidal position buffers are ignored."""
+def read_seq2seq_checkpoint(path, dtype, accept):
+    """The body of the checkpoint loaders: a fairseq-layout file -> (AVHubertSeq2Seq in eval mode, cfg.task or None, the model's
+    state-dict keys the file lacks).  `accept(modalities)` sees cfg.task.modalities (a list of names, or None when the file has
+    none) before anything is built and raises to refuse the file; a file may lack only `mask_emb` and the audio sub-model."""
     ck = torch.load(path, map_location="cpu", weights_only=False)
     m = cfg_get(ck.get("cfg"), "model", None) if ck.get("cfg") is not None else ck.get("args")
     if m is None:
         raise ValueError(f"{path}: neither cfg.model nor args")
-    mods = cfg_get(cfg_get(ck.get("cfg"), "task", None), "modalities", None)
-    if mods is not None and [str(x) for x in mods] != ["video"]:
-        raise NotImplementedError(f"modalities = {list(mods)}: the lip reader takes video only")
+    task = cfg_get(ck.get("cfg"), "task", None)
+    mods = cfg_get(task, "modalities", None)
+    accept(None if mods is None else [str(x) for x in mods])
     w2v = AVHubertConfig.from_w2v_args(cfg_get(m, "w2v_args", None))
     sd = ck["model"]
     cfg = DecoderConfig.from_model_cfg(m, w2v.encoder_embed_dim)
@@ -344,15 +344,26 @@ def load_lip_reader(path, dtype=ops.F16):
     if missing or unexpected:
         raise ValueError(f"{path}: missing {missing[:5]}, unexpected {unexpected[:5]}")
     model.load_state_dict(sd, strict=False)
-    return model.eval()
+    return model.eval(), task, [k for k in own if k not in sd]
 
 
-def save_checkpoint(model, path, w2v_cfg):
-    """Writes `model` in the fairseq layout load_lip_reader reads (cfg.model as plain dicts)."""
+def load_lip_reader(path, dtype=ops.F16):
+    """A fine-tuned AV-HuBERT seq2seq checkpoint (fairseq layout: `cfg.model` or old-style `args`, `model`) -> AVHubertSeq2Seq in
+    eval mode.  The encoder is sized from the pre-training config the checkpoint embeds (`w2v_args`), the decoder from the
+    fine-tuning fields, the vocabulary from `decoder.embed_tokens.weight`.  Sinusoidal position buffers are ignored."""
+    def accept(mods):
+        if mods is not None and mods != ["video"]:
+            raise NotImplementedError(f"modalities = {mods}: the lip reader takes video only")
+    return read_seq2seq_checkpoint(path, dtype, accept)[0]
+
+
+def save_checkpoint(model, path, w2v_cfg, modalities=("video",), task=None):
+    """Writes `model` in the fairseq layout load_lip_reader reads (cfg.model as plain dicts).  modalities: cfg.task.modalities;
+    task: further cfg.task fields (stack_order_audio, normalize) for av_recogniser.load_speech_recogniser."""
     from dataclasses import asdict
     m = {k: v for k, v in asdict(model.cfg).items() if k != "encoder_embed_dim"}
     m["w2v_args"] = {"model": asdict(w2v_cfg)}
-    torch.save({"cfg": {"model": m, "task": {"modalities": ["video"]}},
+    torch.save({"cfg": {"model": m, "task": {"modalities": list(modalities), **(task or {})}},
                 "model": {k: v.detach().cpu() for k, v in model.state_dict().items()}}, path)
 
 

@@ -593,6 +593,32 @@ def stft_mel(wav, mel, basis, fb, fb_range, *, B, S, T_rows, n_fft, hop, pad, ma
         flops=2.0 * frames * n_fft * n_fft, nbytes=float(B) * S * wav.element_size() + 4.0 * frames * n_mels + 4.0 * n_fft * n_fft)
 
 
+def logfbank(wav, out, basis, fb, fb_range, *, B, S, T_rows, stack=4, normalize=True, n_samples=None, n_rows=None, ldw=None, ldo=None):
+    """Log filterbank rows for AV-HuBERT's audio sub-model in one launch (csrc/logfbank.hip; audio.LogFbank builds the tables):
+    wav int16 or fp32 at int16 scale [B, S] -> out fp32 / f16 / bf16 [B, T_rows, 26 * stack] with row stride ldo, every clip
+    analysed alone against n_samples[b] (int32 device tensor; None = S).  Clip b's rows at or past min(its own row count,
+    n_rows[b]) are zeros (n_rows: int32 device tensor, the video's frame counts; None = the audio's own)."""
+    if wav.dtype not in (torch.float32, torch.int16):
+        raise L2SError(f"wav: expected float32 or int16, got {wav.dtype}")
+    for name, t in (("n_samples", n_samples), ("n_rows", n_rows)):
+        if t is not None and (_req(t, None, name).dtype != torch.int32 or t.numel() < B):
+            raise L2SError(f"logfbank: {name} must be int32 [B]")
+    _req(wav, None, "wav"), _req(out, None, "out"), _req(basis, torch.float32, "basis"), _req(fb, torch.float32, "fb")
+    _req(fb_range, torch.int32, "fb_range")
+    C = 26 * stack
+    ldw = ldw if ldw is not None else S
+    ldo = ldo if ldo is not None else C
+    if B > 0 and T_rows > 0 and ((B - 1) * ldw + S > _extent(wav) or ((B * T_rows - 1) * ldo + C) > _extent(out)):
+        raise L2SError("logfbank: wav smaller than [B, ldw] or out smaller than [B, T_rows, ldo]")
+    if basis.numel() < 400 * 512 or fb.numel() < 26 * 257 or fb_range.numel() < 2 * 26:
+        raise L2SError("logfbank: tables smaller than [400, 512], [26, 257], [26, 2]")
+    frames = float(B) * T_rows * stack
+    _run("l2s_logfbank", lambda: _lib.load().l2s_logfbank(
+        _ptr(wav), int(wav.dtype == torch.int16), ldw, _ptr(n_samples), B, S, _ptr(basis), _ptr(fb), _ptr(fb_range), _ptr(n_rows),
+        _ptr(out), dtype_code(out.dtype), ldo, T_rows, stack, int(bool(normalize)), _stream()),
+        flops=2.0 * frames * 400 * 512, nbytes=float(B) * S * wav.element_size() + float(out.element_size()) * B * T_rows * C + 4.0 * 400 * 512)
+
+
 def unit_ce(logits, target, nll, smooth, n_correct, n_tok, *, B, T2, V, ldl=None, ldt=None, lens=None, len_mul=2, pad_idx=1,
             ignore_prefix=0):
     """Label-smoothed cross-entropy sums and accuracy counts per clip in one pass over fp32 logits [B*T2, ldl] (csrc/criterion.hip):
@@ -1489,6 +1515,8 @@ _SCHEMAS = {
                     "Tensor max_len, Tensor emb, Tensor pos_table, Tensor(n!) x_next, Tensor(o!) step, Tensor(p!) n_active, *, int B, "
                     "int beam, int V, int d, int eos, int pad, float embed_scale=1.0, float lenpen=1.0, bool normalize_scores=True, "
                     "int? lde=None, int? ldx=None, int dtype=0) -> ()",
+    "logfbank": "(Tensor wav, Tensor(a!) out, Tensor basis, Tensor fb, Tensor fb_range, *, int B, int S, int T_rows, int stack=4, "
+                "bool normalize=True, Tensor? n_samples=None, Tensor? n_rows=None, int? ldw=None, int? ldo=None) -> ()",
 }
 # C-ABI entry each operator launches (tests/test_torchlib_cpu.py: every device entry of include/lip2speech_hip.h has a twin)
 ENTRY_OF = {n: "l2s_" + n for n in _SCHEMAS}
