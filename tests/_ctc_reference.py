@@ -68,10 +68,12 @@ def _ext(m, c, lp):
     return np.float32(lp + m.sc)
 
 
-def beam_search(probs, beam=30, cutoff_top_n=40, blank=0, fresh_ids=False):
+def beam_search(probs, beam=30, cutoff_top_n=40, blank=0, fresh_ids=False, trace=None):
     """probs [T, V] float32 (softmax output).  Returns the final beam best first: list of (labels tuple, score) with
     score = ctcdecode's beam score (-log p).  fresh_ids=True gives every surviving extension a new node (the WRONG scheme:
-    a revived prefix no longer merges - kept to show the test data exercises the revival path)."""
+    a revived prefix no longer merges - kept to show the test data exercises the revival path).  trace: a list that receives, per
+    frame, the best beam + 1 candidates in order as (score, "own" / "ext", log p of the extending class or None, member index): what
+    a caller needs to show that every survivor, and the first candidate dropped, is decided by a gap or by an exact tie."""
     probs = np.asarray(probs, np.float32)
     T, V = probs.shape
     K = min(cutoff_top_n, V)
@@ -106,6 +108,8 @@ def beam_search(probs, beam=30, cutoff_top_n=40, blank=0, fresh_ids=False):
                 nbv = _ext(m, c, lp)
                 cands.append((_key(nbv, c, s + 1 + k), ("ext", i, c, nbv)))
         cands.sort(key=lambda x: -x[0])
+        if trace is not None:
+            trace.append([(lse(cd[2], cd[3]), "own", None, cd[1]) if cd[0] == "own" else (cd[3], "ext", rank[cd[2]], cd[1]) for _, cd in cands[:beam + 1]])
         nxt = []
         for _, cand in cands[:beam]:
             if cand[0] == "own":
